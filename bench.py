@@ -127,6 +127,8 @@ def single_process(args, n, W, H, seed):
         M.render_frame(poses[k % len(poses)])
     M.sync()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, M.download(H, W))
     kern = [M.rank_timing(r, reset=True) for r in range(args.gpus)]
     dropped = [M.rank_frames_dropped(r) - dropped0[r] for r in range(args.gpus)]     # frames a rank's device skipped inside the timed region
     M.render_frame(cam_c)
@@ -166,18 +168,46 @@ def single_process(args, n, W, H, seed):
 
 SETTLE_FRAMES = 200     # see the timed loop
 
+DUMP_BUDGET_BYTES = 48 << 20     # --dump-outputs: at most this much is written (the contract's ceiling is 64 MB)
+DUMP_SAMPLE_SEED = 20240601
+
+
+def dump_outputs(out_dir, argb):
+    """--dump-outputs DIR: the frame the timed path rendered in its last step (H x W 0xAARRGGBB u32, what a caller of
+    render_to_buffer receives), as DIR/frame_argb.npy -- float32 (H, W, 4), channels A, R, G, B, each 0..255.  A frame
+    larger than the budget is written as a fixed sample instead: DIR/frame_argb.npy (k, 4) for the pixels whose row-major
+    indices DIR/frame_pixel_index.npy (float64, sorted, drawn once with DUMP_SAMPLE_SEED) lists.  Same arguments, same
+    files: the inputs are seeded, so two builds can be compared output for output."""
+    a = np.ascontiguousarray(argb).view(np.uint32)
+    h, w = a.shape
+    flat = a.reshape(-1)
+    os.makedirs(out_dir, exist_ok=True)
+    if flat.size * 16 > DUMP_BUDGET_BYTES:             # 4 float32 per pixel, and room for the float64 index
+        k = DUMP_BUDGET_BYTES // 24
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(flat.size, size=k, replace=False))
+        flat = flat[idx]
+        np.save(os.path.join(out_dir, "frame_pixel_index.npy"), idx.astype(np.float64))
+    ch = np.stack([(flat >> s) & 255 for s in (24, 16, 8, 0)], -1).astype(np.float32)
+    if ch.shape[0] == h * w:
+        ch = ch.reshape(h, w, 4)
+    np.save(os.path.join(out_dir, "frame_argb.npy"), ch)
+
 
 def self_launch(args):
     """`python bench.py --gpus N` without a launcher around it (no WORLD_SIZE): re-execute this very command line as
     `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free> bench.py ...`
     -- one rank per GPU over RCCL, the same processes the driver's own torchrun line starts.  A box with fewer GPUs than
-    N runs only with SPLAT_BENCH_SHARE_GPU=1 (every rank on device 0, gloo: the decomposition, not a measurement)."""
+    N runs only with SPLAT_BENCH_SHARE_GPU=1 (every rank on device 0, gloo: the decomposition, not a measurement).
+    The launch is a child process and this one never opens the GPU itself (the device count comes from a short-lived
+    child of its own), so the ranks are the only processes holding a device while they run."""
     import socket
-    import torch
-    have = torch.cuda.device_count()
-    if have < args.gpus and os.environ.get("SPLAT_BENCH_SHARE_GPU") != "1":
-        sys.exit("bench.py --gpus %d: this box has %d GPU(s) (SPLAT_BENCH_SHARE_GPU=1 runs the %d ranks on device 0 "
-                 "over gloo, to exercise the decomposition)" % (args.gpus, have, args.gpus))
+    import subprocess
+    if os.environ.get("SPLAT_BENCH_SHARE_GPU") != "1":
+        have = int(subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.device_count())"],
+                                  capture_output=True, text=True, check=True).stdout.split()[-1])
+        if have < args.gpus:
+            sys.exit("bench.py --gpus %d: this box has %d GPU(s) (SPLAT_BENCH_SHARE_GPU=1 runs the %d ranks on device 0 "
+                     "over gloo, to exercise the decomposition)" % (args.gpus, have, args.gpus))
     with socket.socket() as so:
         so.bind(("127.0.0.1", 0))
         port = so.getsockname()[1]
@@ -187,7 +217,7 @@ def self_launch(args):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
-    os.execvpe(sys.executable, cmd, env)
+    sys.exit(subprocess.call(cmd, env=env))
 
 
 def surface_leg(R0, image, stream, device, args, counted, leg_drops):
@@ -413,12 +443,17 @@ def main():
                     help="do not run the two short rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of this workload after the timed "
                          "region; roofline.traffic then comes from the committed profiles/traffic.json, labelled so")
     ap.add_argument("--pmc-json", default=None, help="also write the live counter passes' per-kernel bytes to this file")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the frame the last timed step rendered to DIR as float32 .npy "
+                         "(see dump_outputs; rank 0 only)")
     ap.add_argument("--settle", type=int, default=SETTLE_FRAMES, help=argparse.SUPPRESS)
     ap.add_argument("--scene", default=None,
                     help="an INRIA 3DGS .ply (e.g. the real 'truck' / 'bicycle' / plush_sledge scene: none is in the repo, "
                          "src/main.rs:21 loads one): rendered at --workload's resolution and camera instead of the synthetic "
                          "stand-in of the same size; load_from_ply's activations and recentring included (src/gaussians.rs:375-405)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -429,13 +464,13 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
+    if world == 1 and args.gpus > 1 and not args.single_process:
+        return self_launch(args)              # plain `python bench.py --gpus N`: run as the torchrun launch of N ranks
     if not torch.cuda.is_available():
         sys.exit("bench.py needs a GPU (the HIP path has no CPU fallback)")
     if args.single_process and world == 1 and args.gpus > 1:
         return single_process(args, n, W, H, seed)
     if world != args.gpus:
-        if world == 1 and args.gpus > 1:
-            return self_launch(args)          # plain `python bench.py --gpus N`: become the torchrun launch of N ranks
         args.gpus = world
     # SPLAT_BENCH_SHARE_GPU=1 (testing only): all ranks on cuda:0 over gloo, to exercise the N>1 code
     # path on a single-GPU box (RCCL refuses ranks that share a device); the real run is one rank per GPU over RCCL
@@ -585,6 +620,8 @@ def main():
     key_entries = R.binning_mode()
     last_pose = poses[(frame_no[0] - 1) % len(poses)]
     final = images[(frame_no[0] - 1) % len(images)].clone()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, final.cpu().numpy())
     # the compositor's (wave, record) iteration counts of a frame LIKE THE TIMED ONES (the first frame above scanned for its
     # walks' starts; the frames of a camera at rest start where the previous frame did: SPLAT_OPT_START_HINTS)
     with torch.cuda.stream(stream):

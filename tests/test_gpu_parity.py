@@ -670,8 +670,9 @@ def test_bench_multirank_path_on_shared_gpu():
 
 def test_bench_launches_its_own_ranks():
     """`python bench.py --gpus N` WITHOUT a launcher around it (how the driver's N=1 command line looks with another N)
-    must print the line itself: bench.py re-executes as the torchrun launch of N ranks.  C3 -- BASELINE config 4 at
-    workload size -- as 8 ranks sharing this GPU (gloo transport), and the one-process form (splat_multi_*) as 4."""
+    must print the line itself: bench.py starts the torchrun launch of N ranks as its child.  C3 -- BASELINE config 4 at
+    workload size -- as 4 ranks sharing this GPU (gloo transport), and the one-process form (splat_multi_*) as 8 (at most
+    six processes may hold the GPU at once, this one included)."""
     import json
     import os
     import subprocess
@@ -679,7 +680,7 @@ def test_bench_launches_its_own_ranks():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, SPLAT_BENCH_SHARE_GPU="1")
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
-    for extra, n in ((["--gpus", "8"], 8), (["--gpus", "4", "--single-process"], 4)):
+    for extra, n in ((["--gpus", "4"], 4), (["--gpus", "8", "--single-process"], 8)):
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--workload", "C3"] + extra,
                            capture_output=True, text=True, timeout=1200, env=env, cwd=root)
         assert r.returncode == 0, "\n".join([l for l in r.stderr.splitlines() if any(w in l.lower() for w in ("fault", "abort", "error", "assert", "terminate", "what()", "hsa"))][:40]) + r.stderr[-1500:]

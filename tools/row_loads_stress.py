@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """splat_tile_row_loads under contention: k processes on one GPU, each asks for the C3 frame's per-tile-row pair counts again and
-again (between frames, as bench.py's ranks do once) -- every answer must be the same.  usage: row_loads_stress.py [procs] [rounds]"""
+again (between frames, as bench.py's ranks do once) -- every answer must be the same.  usage: row_loads_stress.py [procs] [rounds]
+(procs <= 6: no more processes than that may hold the GPU at once)"""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if len(sys.argv) > 1 and sys.argv[1] == "--child":
@@ -24,7 +25,9 @@ if len(sys.argv) > 1 and sys.argv[1] == "--child":
             R.sync()
     print("pid %d: total %d, %d of %d answers differ" % (os.getpid(), int(first.sum()), bad, rounds), flush=True)
     sys.exit(1 if bad or int(first.sum()) != 8025623 else 0)
-procs = int(sys.argv[1]) if len(sys.argv) > 1 else 8
+procs = int(sys.argv[1]) if len(sys.argv) > 1 else 6
+if not 1 <= procs <= 6:
+    sys.exit("row_loads_stress.py: procs must be 1..6 (at most six processes may hold the GPU at once)")
 rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 40
 ps = [subprocess.Popen([sys.executable, os.path.abspath(__file__), "--child", str(rounds)]) for _ in range(procs)]
 rc = [p.wait() for p in ps]
