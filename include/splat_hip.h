@@ -295,6 +295,12 @@ int splat_set_frame_overlap(splat_ctx* ctx, int32_t n);
                                             least this many large splats (half of it to let go again; always when nothing is known
                                             or behind a camera jump): the list's kernel is one more launch on a small frame's chain.
                                             0 = always, -1 = never (default 256; SPLAT_LARGE_LIST_MIN; include/splat_policy.h)        */
+#define SPLAT_OPT_START_REFINE 24       /* with a camera at rest (SPLAT_OPT_START_HINTS 1 or 2) the compositor's waves refine where
+                                            their exact walks start: half of the tiles a frame try a shallower start than the one
+                                            that closed last, keep it where the bracket closes and walk again from the old one where it
+                                            does not (those waves are not counted as n_fallback).  Exactness never rests on it.  Exact modes only (not with
+                                            SPLAT_MODE_FAST, whose frame depends on where a walk starts).
+                                            1 = on (default), 0 = off (SPLAT_START_REFINE)                                         */
 int splat_set_option(splat_ctx* ctx, int32_t option, double value);
 int splat_get_option(const splat_ctx* ctx, int32_t option, double* value);
 void* splat_stream(splat_ctx* ctx);                   /* the hipStream_t the kernels run on */

@@ -31,9 +31,11 @@ extern "C" {
 #define SPLAT_POLICY_REDO_RUN 256        /* moving frames that carry the redo launches once a list has outgrown its region */
 #define SPLAT_POLICY_REDO_JUMP_RUN 8     /* ... and behind a camera jump */
 #define SPLAT_POLICY_PAIR_WALK_RATIO 500 /* pairs per key of the longest list below which the paired walk is taken */
+#define SPLAT_POLICY_NO_REFINE 4         /* knobs.start_hints flag (SPLAT_OPT_START_REFINE 0): a camera at rest keeps its starts as they are */
 
 typedef struct splat_policy_knobs {      /* the context's options that decisions depend on (SPLAT_OPT_*) */
-    int32_t start_hints;                 /* SPLAT_OPT_START_HINTS 0..2 */
+    int32_t start_hints;                 /* SPLAT_OPT_START_HINTS 0..2, | SPLAT_POLICY_NO_REFINE (the structs' sizes are the
+                                            interface: the option rides in a flag bit instead of a field of its own) */
     int32_t count_first;                 /* SPLAT_OPT_COUNT_FIRST 0..2 */
     int32_t overflow_redo;               /* SPLAT_OPT_OVERFLOW_REDO 0..2 */
     int32_t early_min;                   /* SPLAT_OPT_EARLY_OUT_MIN_LIST */
@@ -112,7 +114,9 @@ typedef struct splat_policy_decision {
     int32_t use_large_list;              /* K1 lists its large splats and bin_large_kernel bins them tile by tile (else K1 expands them itself) */
     int32_t layout_radius;               /* tiles: the regions this frame's scan builds (for the frame two on) are sized from the longest
                                             list within this distance of each tile; 0 = from the tile's own list (camera at rest, a jump) */
-    int32_t reserved;
+    uint32_t refine;                     /* != 0 (at rest only): the compositor's waves refine their starts -- half of the tiles
+                                            probe a shallower one each frame.  Bits 16..31: the rest's tag (bit 31 set; from the camera
+                                            hash: a camera that moved makes every wave's probe state fresh again), bits 0..15: the frame */
     splat_policy_state next;
 } splat_policy_decision;
 

@@ -33,6 +33,7 @@ constexpr int N_TIMES = 6;     // preprocess, scan, emit, sort, composite, statu
 constexpr int EV_RING = 32;
 static_assert(EV_RING == SPLAT_POLICY_RING, "the frame policy sees the whole status ring");
 constexpr int N_SLOTS = 4;
+constexpr unsigned int HINT_WORDS = 13u;   // per tile (need_hint): 4 walks' needs, the selection's depth, 4 walks' starts, 4 starts' refinement states
 
 struct EvSet {
     hipEvent_t e[N_EV];
@@ -211,7 +212,9 @@ struct splat_ctx {
     int start_hints = 2;                   // SPLAT_OPT_START_HINTS / SPLAT_START_HINTS: 0 the compositor scans for its walks' starts on every frame; 1 not with
                                            // a camera at rest; 2 nor, three frames of four, with one in slow motion (see enqueue_frame)
     bool one_pass_select = true;           // SPLAT_DBG_ONE_PASS_SELECT=0: near selection always takes its two passes (histogram, compaction)
+    int start_refine = 1;                  // SPLAT_OPT_START_REFINE / SPLAT_START_REFINE: a camera at rest refines its walks' starts (splat_policy_decision::refine)
     unsigned int* need_hint = nullptr;     // 4 x m_alloc words: per tile and wave, the nearest keys its walk needed in the most recent frame
+                                           // (HINT_WORDS x m_alloc in all: the selections' depths, the walks' starts and their refinement behind them)
     bool last_near = false;                // the most recent frame ran with near selection: its long lists are unordered in memory
     int timing_every = 8;                  // SPLAT_TIMING_EVERY: per-kernel events on every n-th frame (and whenever stats are asked for)
     int pipeline = 6;                      // frames in flight on the device (SPLAT_PIPELINE = 1..6, see enqueue_frame)
@@ -528,8 +531,8 @@ int ensure_bins(splat_ctx* c, unsigned int m) {
     HIP_TRY(c, dmalloc(c, &c->zero_layout, sizeof(unsigned int) * (size_t)(m + 1)));
     HIP_TRY(c, fill_now(c->zero_layout, 0, sizeof(unsigned int) * (size_t)(m + 1)));
     dfree(c->need_hint);
-    HIP_TRY(c, dmalloc(c, &c->need_hint, sizeof(unsigned int) * 9u * (size_t)(m + 1)));      // (+ one word per tile behind them: the depth its last selection began at; + four: where its waves' walks started)
-    HIP_TRY(c, fill_now(c->need_hint, 0, sizeof(unsigned int) * 9u * (size_t)(m + 1)));
+    HIP_TRY(c, dmalloc(c, &c->need_hint, sizeof(unsigned int) * HINT_WORDS * (size_t)(m + 1)));      // (+ one word per tile behind them: the depth its last selection began at; + four: where its waves' walks started; + four: their refinement)
+    HIP_TRY(c, fill_now(c->need_hint, 0, sizeof(unsigned int) * HINT_WORDS * (size_t)(m + 1)));
     for (Slot& s : c->slots) {
         dfree(s.counts); dfree(s.offsets); dfree(s.cursor); dfree(s.order); dfree(s.lens); dfree(s.counts_b); dfree(s.lay_a); dfree(s.lay_b);
         dfree(s.near_m); dfree(s.redo_layout); dfree(s.redo_cursors); dfree(s.off2);
@@ -715,7 +718,7 @@ int enqueue_frame(splat_ctx* c, uint32_t* d_argb, bool timed, bool want_iters = 
     splat_policy_decision pd;
     {
         splat_policy_knobs pk;
-        pk.start_hints = c->start_hints; pk.count_first = c->count_first; pk.overflow_redo = c->overflow_redo; pk.early_min = c->early_min;
+        pk.start_hints = c->start_hints | (c->start_refine ? 0 : SPLAT_POLICY_NO_REFINE); pk.count_first = c->count_first; pk.overflow_redo = c->overflow_redo; pk.early_min = c->early_min;
         pk.early_eps = c->early_eps; pk.near_cap = c->near_cap; pk.fused_sort_max = c->fused_sort_max; pk.sort_in_comp = c->sort_in_comp;
         pk.pair_mode = c->pair_mode; pk.pipeline = c->pipeline; pk.tight_grids = c->tight_grids ? 1 : 0;
         pk.large_list_min = c->large_tiles < 0 ? -1 : c->large_list_min; pk.layout_motion = c->layout_motion;
@@ -906,7 +909,9 @@ int enqueue_frame(splat_ctx* c, uint32_t* d_argb, bool timed, bool want_iters = 
     const bool pair_walk = pd.pair_walk != 0;
     launch_composite(cs, m, c->fc, s.offsets, s.order, s.lens, s.keys, s.recs, d_argb, d_st, c->orig, c->fused_sort_max, iters, want_iters,
                      pair_walk, (c->cfg.mode & SPLAT_MODE_LIBM_EXP) != 0, c->clear_first, comp_sorts ? s.keys2 : nullptr, near_cap ? s.near_m : nullptr,
-                     c->need_hint, c->need_hint ? c->need_hint + 5u * (size_t)c->m_alloc : nullptr, off2);
+                     c->need_hint, c->need_hint ? c->need_hint + 5u * (size_t)c->m_alloc : nullptr, off2,
+                     c->need_hint ? c->need_hint + 9u * (size_t)c->m_alloc : nullptr,
+                     c->fc.close_width == 0.0f ? pd.refine : 0u);      // (exact modes only: a fast-mode frame depends on where its walks start)
     c->last_near = near_cap != 0u;
     HIP_TRY(c, mark(6, cs));
     // the scan has already delivered this frame's status to h_status[r]; a statistics frame refreshes it with the late
@@ -1020,7 +1025,7 @@ int prepare_binning(splat_ctx* c, unsigned int m, FrameConst* fc) {
             sl.layout_valid = false; sl.flip = 0;
             if (sl.counts) HIP_TRY(c, hipMemsetAsync(sl.counts, 0, sizeof(unsigned int) * (size_t)(m + 1), c->stream));
         }
-        if (c->need_hint) HIP_TRY(c, hipMemsetAsync(c->need_hint, 0, sizeof(unsigned int) * 9u * (size_t)c->m_alloc, c->stream));   // another grid: another tile under every index
+        if (c->need_hint) HIP_TRY(c, hipMemsetAsync(c->need_hint, 0, sizeof(unsigned int) * HINT_WORDS * (size_t)c->m_alloc, c->stream));   // another grid: another tile under every index
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         c->last_one_pass = one_pass; c->layout_m = m;
         reset_policy(c);
@@ -1209,6 +1214,7 @@ bool store_option(splat_ctx* c, int opt, double v, bool dry = false) {
         case SPLAT_OPT_KEYS_PER_GAUSSIAN: if (v != 0.0 && (v < 4.0 || v > 256.0)) return false; SPLAT_DRY_; c->keys_per_gaussian = (unsigned int)v; return true;
         case SPLAT_OPT_LARGE_SPLAT_TILES: if (v < -1.0 || v > 1048576.0 || v != std::floor(v)) return false; SPLAT_DRY_; c->large_tiles = (int)v; return true;
         case SPLAT_OPT_LARGE_LIST_MIN: if (v < -1.0 || v > 1e9 || v != std::floor(v)) return false; SPLAT_DRY_; c->large_list_min = (int)v; return true;
+        case SPLAT_OPT_START_REFINE: if (v != 0.0 && v != 1.0) return false; SPLAT_DRY_; c->start_refine = (int)v; return true;
         default: return false;
     }
 #undef SPLAT_DRY_
@@ -1238,6 +1244,7 @@ bool load_option(const splat_ctx* c, int opt, double* v) {
         case SPLAT_OPT_COUNT_FIRST: *v = c->count_first; return true;
         case SPLAT_OPT_LARGE_SPLAT_TILES: *v = c->large_tiles; return true;
         case SPLAT_OPT_LARGE_LIST_MIN: *v = c->large_list_min; return true;
+        case SPLAT_OPT_START_REFINE: *v = c->start_refine; return true;
         default: return false;
     }
 }
@@ -1326,6 +1333,7 @@ int splat_create(const splat_config* cfg, splat_ctx** out) {
     }
     option_from_env(c, SPLAT_OPT_LARGE_SPLAT_TILES, "SPLAT_LARGE_TILES", -1, 1048576);
     option_from_env(c, SPLAT_OPT_LARGE_LIST_MIN, "SPLAT_LARGE_LIST_MIN", -1, 1e9);
+    option_from_env(c, SPLAT_OPT_START_REFINE, "SPLAT_START_REFINE", 0, 1);
     if (const char* lm = std::getenv("SPLAT_LAYOUT_MOTION")) c->layout_motion = std::atoi(lm) != 0 ? 1 : 0;
     if (const char* k1 = std::getenv("SPLAT_SORT_RADIX_MIN")) c->knobs.sort_radix_min = (unsigned int)std::max(0, std::atoi(k1));
     if (const char* k2 = std::getenv("SPLAT_SCAN_THREADS")) c->knobs.scan_threads = std::atoi(k2);
@@ -1458,7 +1466,7 @@ int splat_set_option(splat_ctx* c, int32_t option, double value) {
     if (!store_option(c, option, value)) return fail(c, SPLAT_ERR_INVALID, "option value out of range");
     // (another selection size: what the tiles' walks needed under the old one is forgotten)
     if (option == SPLAT_OPT_NEAR_SELECT_KEYS && c->need_hint && c->m_alloc)
-        HIP_TRY(c, fill_now(c->need_hint, 0, sizeof(unsigned int) * 9u * (size_t)c->m_alloc));
+        HIP_TRY(c, fill_now(c->need_hint, 0, sizeof(unsigned int) * HINT_WORDS * (size_t)c->m_alloc));
     // (the large list switched on with a scene in place: its buffers exist from now on -- splat_upload_scene makes them otherwise)
     if (option == SPLAT_OPT_LARGE_SPLAT_TILES && c->large_tiles >= 0 && c->n != 0)
         for (Slot& sl : c->slots)
@@ -1541,7 +1549,7 @@ int splat_upload_scene(splat_ctx* c, uint64_t n, const float* pos4, const float*
     for (Slot& sl : c->slots) sl.layout_valid = false;
     c->sort_hint = false;
     // another scene under every tile: what the walks of the old one needed says nothing (near selection, start hints)
-    if (c->need_hint && c->m_alloc) (void)fill_now(c->need_hint, 0, sizeof(unsigned int) * 9u * (size_t)c->m_alloc);
+    if (c->need_hint && c->m_alloc) (void)fill_now(c->need_hint, 0, sizeof(unsigned int) * HINT_WORDS * (size_t)c->m_alloc);
     reset_policy(c);
     // The per-tile arrays (a few hundred KB per frame slot at 4K) exist before the first frame as well: fifty small allocations
     // and six synchronous fills were a third of its call.  A larger target than 3840 x 2160 makes them again, as always.
@@ -1595,7 +1603,7 @@ int splat_set_slab(splat_ctx* c, int32_t tile_row0, int32_t tile_row1) {
     for (Slot& sl : c->slots) sl.layout_valid = false;
     c->sort_hint = false;
     c->hint_pairs = 0; c->hint_maxlen = 0;
-    if (c->need_hint && c->m_alloc) (void)hipMemsetAsync(c->need_hint, 0, sizeof(unsigned int) * 9u * (size_t)c->m_alloc, c->stream);
+    if (c->need_hint && c->m_alloc) (void)hipMemsetAsync(c->need_hint, 0, sizeof(unsigned int) * HINT_WORDS * (size_t)c->m_alloc, c->stream);
     c->slab0 = tile_row0; c->slab1 = tile_row1;
     reset_policy(c);
     return rc;
@@ -2005,6 +2013,14 @@ int splat_debug_near_state(splat_ctx* c, unsigned int* lens, unsigned int* near_
     ok = ok && hipMemcpy(near_m, s.near_m, sizeof(unsigned int) * m, hipMemcpyDeviceToHost) == hipSuccess;
     ok = ok && hipMemcpy(need_hint, c->need_hint, sizeof(unsigned int) * 4u * m, hipMemcpyDeviceToHost) == hipSuccess;
     return ok ? SPLAT_OK : SPLAT_ERR_HIP;
+}
+
+// (debug, not part of the ABI)  Waves of the last harvested statistics frame whose start-refinement probe did not close its
+// bracket and walked again from the known-good start (FrameStatus::n_probe_fail; not among splat_stats::n_fallback).
+int splat_debug_probe_failures(splat_ctx* c, uint64_t* n) {
+    if (!c || !n || c->last_slot < 0) return SPLAT_ERR_INVALID;
+    *n = c->last.n_probe_fail;
+    return SPLAT_OK;
 }
 
 int64_t splat_binning_mode(splat_ctx* c) {

@@ -88,6 +88,9 @@ struct FrameStatus {
     unsigned int redone;                // 1: the frame outgrew its regions and was binned again on the device (overflow redo); written by every scan
     unsigned int n_long_keys;           // one-pass binning: entries of the second key buffer the frame's lists of more than 2048 keys ask for
     unsigned int arrived;               // 1: the frame's scan has written this status (the host zeroes its copy when it enqueues the frame)
+    unsigned int n_probe_fail;          // waves whose refinement probe (a shallower start at rest) did not close and walked again from the
+                                        // known-good start -- not among n_fallback
+    unsigned int pad_;                  // (n_blocks_culled is 8-byte aligned)
     unsigned long long n_blocks_culled; // K1 blocks skipped by the bounds test (filled on the host from the block flags)
     unsigned long long layout_total;    // one-pass binning: key-buffer entries the regions built from this frame ask for (layout_kernel)
 };
@@ -192,7 +195,10 @@ void launch_composite(hipStream_t s, unsigned int n_tiles, FrameConst fc, const 
                                                            keys each wave's walk needed (sizes the next frame's selection) */,
                       unsigned int* start_hint = nullptr /* 4 words per tile, kept from frame to frame: where each wave's exact walk
                                                             started, in keys from the list's near end (fc.start_hints) */,
-                      const unsigned int* off2 = nullptr /* see launch_sort */);
+                      const unsigned int* off2 = nullptr /* see launch_sort */,
+                      unsigned int* probe_hint = nullptr /* 4 words per tile beside start_hint, kept from frame to frame: each wave's
+                                                            start refinement at rest (composite_tile, phase A) */,
+                      unsigned int refine = 0u /* != 0: this frame's waves refine their starts (splat_policy_decision::refine) */);
 hipError_t init_device_kernels();   // per-device kernel attributes; call with the device current
 
 // ---- splat_multi.hip: the multi-GPU layer's hooks into a context (splat_ctx itself stays private to splat_api.hip)

@@ -1234,7 +1234,7 @@ __global__ __launch_bounds__(1024) void scan_kernel(unsigned int m, unsigned int
         const unsigned int ge16384 = start[cls_of(16384u)] + hist[cls_of(16384u)];
         status->n_ge8192 = ge8192; status->n_ge2048 = ge2048; status->n_ge16384 = ge16384;
         if (status->overflow == 0 && (ge8192 > grid_big || ge2048 > grid_mid || ge16384 > grid_long)) status->overflow = 3u;
-        status->n_fallback = 0; status->n_sort_fallback = 0; status->n_near_tiles = 0; status->n_near_fallback = 0; status->n_large = 0; status->n_window = 0;
+        status->n_fallback = 0; status->n_probe_fail = 0; status->n_sort_fallback = 0; status->n_near_tiles = 0; status->n_near_fallback = 0; status->n_large = 0; status->n_window = 0;
         status->redone = 0u;                          // (the ring entry may have carried a redone one-pass frame before)
         status->arrived = 1u;
         if (host_status) *host_status = *status;      // (n_visible / n_singular: K1's atomics, complete before this kernel)
@@ -1545,7 +1545,7 @@ __global__ __launch_bounds__(SCAN_NT) void scan_bucket_kernel(unsigned int m, un
         if (off2 != nullptr && pool2 > cap2 && status->overflow == 0u) status->overflow = 4u;
         // this kernel initialises the frame's status (nothing before it in a one-pass frame touches it) ...
         status->n_visible = 0; status->n_singular = 0;
-        status->n_fallback = 0; status->n_sort_fallback = 0; status->n_near_tiles = 0; status->n_near_fallback = 0; status->n_large = n_large_seen; status->n_window = n_window_seen;
+        status->n_fallback = 0; status->n_probe_fail = 0; status->n_sort_fallback = 0; status->n_near_tiles = 0; status->n_near_fallback = 0; status->n_large = n_large_seen; status->n_window = n_window_seen;
         status->redone = redo_only ? 1u : 0u;  // (1: this frame outgrew its regions and was binned again on the device)
         status->n_blocks_culled = 0;
         // ... and delivers it to the host: everything an asynchronous frame reports is decided here (layout_total, the
@@ -2572,6 +2572,9 @@ __device__ __forceinline__ f2 blend_channel2(f2 k, float ia, f2 ac) {
 //            is carried twice, from 0 and from 255; blend() is monotone in the state, so once
 //            lo == hi the result provably does not depend on anything skipped and the walk
 //            continues single-state.  A wave that ends with lo != hi redoes the whole list.
+#ifndef SPLAT_REFINE_MIN_STEP
+#define SPLAT_REFINE_MIN_STEP 8          // start refinement at rest: the smallest step (list positions) a probe takes (composite_tile)
+#endif
 #ifndef SPLAT_COMP_WAVES
 #define SPLAT_COMP_WAVES 1
 #endif
@@ -2587,6 +2590,8 @@ struct CompArgs {
     const unsigned int* orig;
     unsigned long long* keys2; const unsigned int* near_m;
     unsigned int* need_hint; unsigned int* start_hint; const unsigned int* off2;
+    unsigned int* probe_hint;            // 4 words per tile beside start_hint: each wave's start refinement (see phase A); nullptr: none
+    unsigned int refine;                 // != 0: a camera at rest refines its starts this frame -- bits 16..31 the rest's tag, 0..15 the frame
 };
 typedef const __attribute__((address_space(4))) CompArgs* KernArgs;       // (constant address space: uniform scalar loads)
 template <bool PAIR, bool LIBM>
@@ -2904,6 +2909,14 @@ __device__ __forceinline__ void composite_tile(unsigned char* smem, const unsign
     // did then; if it ever did not (a hint from another camera: frames overlap on the device), the retry below takes over
     // as after any scan that stopped short.  Exactness never rests on the hint, only the scan's time does.
     bool scanned = false, hinted = false;
+    // START REFINEMENT (camera at rest, ka->refine != 0).  The hint is where the scan stopped at early_eps (~1e-6), a
+    // conservative start; the bracket usually closes from a shallower one.  Half of the tiles take turns each frame: their
+    // waves walk from `good - step` instead (step: list positions, probe_hint), keep the shallower start when the bracket
+    // closes there, and retry from `good` -- which closed last frame -- when it does not, halving the step.  A step below
+    // SPLAT_REFINE_MIN_STEP is converged (0): a converged start lies within that many positions of one whose bracket stays open.
+    // The probe word carries the rest's tag (bits 16..31), so that a camera that moved resets it.
+    // probe: 0 no probe; else the step, bit 31 once the probe failed.
+    unsigned int probe = 0u;
     if (early && !need_far && fc.start_hints != 0 && start_hint != nullptr) {
         unsigned int h = (unsigned int)__builtin_amdgcn_readfirstlane((int)start_hint[tile * 4u + wave]);
         if (fc.start_hints >= 2 && h != 0u) {
@@ -2911,6 +2924,14 @@ __device__ __forceinline__ void composite_tile(unsigned char* smem, const unsign
             // in very slow motion (under ~0.15 degrees a frame: start_light) half the margin, every eighth frame
             if (fc.start_light) h = (((unsigned int)fc.start_hints + tile) & 7u) == 0u ? 0u : h + (h >> 4) + 16u;
             else h = (((unsigned int)fc.start_hints + tile) & 3u) == 0u ? 0u : h + (h >> 3) + 32u;
+        } else if (h != 0u && h < end - lb && !second_walk) {
+            const KernArgs kr = late();
+            const unsigned int refine = kr->refine;
+            if (refine != 0u && ((refine + tile) & 1u) == 0u) {
+                const unsigned int pw = (unsigned int)__builtin_amdgcn_readfirstlane((int)kr->probe_hint[tile * 4u + wave]);
+                const unsigned int step = (pw >> 16) == (refine >> 16) ? (pw & 0xffffu) : min(max(h >> 2, (unsigned int)SPLAT_REFINE_MIN_STEP), 0xffffu);
+                if (step != 0u && step < h) { probe = step; h -= step; }
+            }
         }
         if (h != 0u) {
             if (h < end - lb) { ws = end - h; hinted = true; }
@@ -3066,8 +3087,17 @@ __device__ __forceinline__ void composite_tile(unsigned char* smem, const unsign
             if (pos < end) run(std::false_type{}, pos);
             break;
         }
-        // lo != hi somewhere at the end of the list: not proven.  Retry from twice the depth
-        // (geometric, so a long list is not redone in full for one stubborn LSB).
+        // lo != hi somewhere at the end of the list: not proven.  A probe retries from the known-good start (counted apart
+        // from the fallbacks: a probe is expected to fail now and then) ...
+        if (probe != 0u && !(probe >> 31)) {
+            probe |= 0x80000000u;
+            const KernArgs kr = late();
+            const unsigned int g = (unsigned int)__builtin_amdgcn_readfirstlane((int)kr->start_hint[tile * 4u + wave]);
+            if (lane == 0) atomicAdd(&kr->status->n_probe_fail, 1u);
+            if (g > end - start && g < end - lb) { start = end - g; continue; }
+            // (the known-good start is not deeper than the probe's -- another frame rewrote it: the doubling retry)
+        }
+        // ... anything else from twice the depth (geometric, so a long list is not redone in full for one stubborn LSB).
         if (lane == 0) atomicAdd(&late()->status->n_fallback, 1ull);
         const unsigned int depth = end - start;
         start = (start - lb > depth) ? start - depth : lb;
@@ -3097,6 +3127,15 @@ __device__ __forceinline__ void composite_tile(unsigned char* smem, const unsign
         unsigned int used = max(end - max(start, lb), 1u);
         if (!has_far && used > (end - beg) - ((end - beg) >> 2)) used = end - beg;     // (most of the list anyway: all of it, without a bracket)
         start_l[tile * 4u + wave] = used;
+    }
+    // ... and a probe's outcome: closed from the shallower start -> that is the new known-good one, the step stays; open -> the
+    // retry above wrote where it closed instead, the step halves
+    if (probe != 0u && lane == 0u) {
+        const bool failed = (probe >> 31) != 0u;
+        const unsigned int half = (probe & 0xffffu) >> 1;
+        const unsigned int step = failed ? (half >= (unsigned int)SPLAT_REFINE_MIN_STEP ? half : 0u) : probe;
+        if (!failed) start_l[tile * 4u + wave] = end - ws;
+        kl->probe_hint[tile * 4u + wave] = (kl->refine & 0xffff0000u) | step;
     }
     if (need_far) return true;
     if (inside)
@@ -3437,7 +3476,8 @@ void launch_composite(hipStream_t s, unsigned int n_tiles, FrameConst fc, const 
                       const unsigned int* order, const unsigned int* lens, unsigned long long* keys, const Rec* recs,
                       uint32_t* argb, FrameStatus* status, const unsigned int* orig, unsigned int fused_sort_max, uint2* iters,
                       bool keep_keys, bool pair_walk, bool libm_exp, bool clear_first, unsigned long long* keys2, const unsigned int* near_m,
-                      unsigned int* need_hint, unsigned int* start_hint, const unsigned int* off2) {
+                      unsigned int* need_hint, unsigned int* start_hint, const unsigned int* off2, unsigned int* probe_hint,
+                      unsigned int refine) {
     if (!n_tiles) return;
     if (!off2) off2 = offsets;
     if (g_knobs->dbg_ntiles) n_tiles = std::min(n_tiles, g_knobs->dbg_ntiles);   // debug: composite only the N longest tiles
@@ -3450,6 +3490,7 @@ void launch_composite(hipStream_t s, unsigned int n_tiles, FrameConst fc, const 
     a.fc = fc; a.offsets = offsets; a.order = order; a.lens = lens; a.keys = keys; a.recs = recs; a.argb = argb; a.status = status;
     a.fused_sort_max = fused_sort_max; a.radix_min = sort_radix_min(); a.iters = iters; a.keep_keys = flags; a.clear_first = clear_first ? 1u : 0u;
     a.orig = orig; a.keys2 = keys2; a.near_m = near_m; a.need_hint = near ? need_hint : nullptr; a.start_hint = start_hint; a.off2 = off2;
+    a.probe_hint = probe_hint; a.refine = (probe_hint != nullptr && start_hint != nullptr) ? refine : 0u;
     auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(n_tiles), dim3(256), pad, s, a); };
     if (near) {         // (a tile the selection does not serve repairs itself: no launch behind this one)
         if (libm_exp) go(composite_exact_kernel<false, true, 2>);

@@ -111,10 +111,19 @@ int splat_policy_decide(const splat_policy_knobs* kp, const splat_policy_state* 
     // they did (1).  The first frames at rest, and a camera that moves fast: scan (0), which also refreshes the hints.  A camera
     // that moved by less than ~half a degree: where they did plus a margin, and every fourth frame the scan, tiles taking turns
     // (>= 2: the frame number rides along).
+    const int hints = k.start_hints & 3;
     int mode = 0;
-    if (k.start_hints >= 1 && st.still_frames >= (uint32_t)SPLAT_POLICY_STILL_FRAMES) mode = 1;
-    else if (k.start_hints >= 2 && st.still_frames == 0u && delta < SPLAT_POLICY_DELTA_SLOW) mode = 2 + (int)(in.frame_idx & 0xffffull);
+    if (hints >= 1 && st.still_frames >= (uint32_t)SPLAT_POLICY_STILL_FRAMES) mode = 1;
+    else if (hints >= 2 && st.still_frames == 0u && delta < SPLAT_POLICY_DELTA_SLOW) mode = 2 + (int)(in.frame_idx & 0xffffull);
     d.start_hints_mode = mode;
+    // ... and at rest the starts are refined: the scan's start is conservative (transmittance 1e-6 on the wave's least opaque
+    // pixel), the bracket closes from a shallower one on most waves; a camera at rest tests one per wave, half of the tiles
+    // a frame, and keeps it where the bracket closed (composite_tile, phase A).  The tag ties the waves' probe state to this
+    // camera: one that moves and stops again starts from fresh steps, with no launch to clear anything.
+    if (mode == 1 && !(k.start_hints & SPLAT_POLICY_NO_REFINE)) {
+        const uint32_t tag = 0x8000u | (uint32_t)((hash ^ (hash >> 15) ^ (hash >> 30) ^ (hash >> 45)) & 0x7fffu);
+        d.refine = (tag << 16) | (uint32_t)(in.frame_idx & 0xffffull);
+    }
     d.start_light = delta < SPLAT_POLICY_DELTA_CREEP ? 1 : 0;
     // how far the image moved since the last frame, in tiles: a rotation by delta radians shifts the centre by focal * delta
     // pixels.  The near selection looks that far around a tile for what its walks may need: 2 tiles for a camera at rest, 7 for a
@@ -124,7 +133,7 @@ int splat_policy_decide(const splat_policy_knobs* kp, const splat_policy_state* 
     // (at rest the scan is paid once, in the first frames after the camera stopped: lists from half the usual length take the
     // early-out then -- 384 instead of 768 keys: C3 3060 -> 3120 frames/s, below that nothing more)
     d.early_min = k.early_min;
-    if (k.start_hints >= 1 && st.still_frames >= 1u) d.early_min = std::min(d.early_min, std::max(k.early_min / 2, 1));
+    if (hints >= 1 && st.still_frames >= 1u) d.early_min = std::min(d.early_min, std::max(k.early_min / 2, 1));
 
     // ---- COUNT FIRST: the frame counts its pairs per tile (K1's count flavour: a third of a K1) and bins into regions that fit
     // exactly ITS camera.  A slot without a layout does; and, by SPLAT_OPT_COUNT_FIRST, (1) the moving frames behind a run of frames
