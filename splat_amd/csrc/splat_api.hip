@@ -578,20 +578,33 @@ int ensure_keys(splat_ctx* c, uint64_t want, uint64_t want2) {
     if (rc != SPLAT_OK) return rc;
     want = std::max(want, c->cap); want2 = std::max(want2, c->cap2);
     const bool grow1 = want > c->cap, grow2 = want2 > c->cap2;
+    // The last frame's lists stay readable (splat_get_tile_lists): a frame whose regions asked for more than the buffer holds
+    // was squeezed into it and is complete, and the growth it asked for comes behind it (finish_frame) -- its slot's keys are
+    // carried into the new buffer.
+    const uint64_t old_cap = c->cap;
+    unsigned long long* kept = nullptr;
+    if (grow1 && c->last_slot >= 0 && old_cap) std::swap(kept, c->slots[c->last_slot].keys);
     if (grow1) { c->cap = 0; for (Slot& s : c->slots) dfree(s.keys); }
     if (grow2) { c->cap2 = 0; for (Slot& s : c->slots) dfree(s.keys2); }
     for (int k = 0; k < slots_in_use(c); ++k) {
         Slot& s = c->slots[k];
         hipError_t e = hipSuccess;
         if (grow1) e = dmalloc(c, &s.keys, sizeof(unsigned long long) * want);
+        if (e == hipSuccess && kept && k == c->last_slot) {
+            e = hipMemcpy(s.keys, kept, sizeof(unsigned long long) * old_cap, hipMemcpyDeviceToDevice);
+            if (e == hipSuccess) e = hipStreamSynchronize(nullptr);      // (the context's streams do not wait for the default stream: fill_now)
+            dfree(kept);
+        }
         if (e == hipSuccess && grow2) e = dmalloc(c, &s.keys2, sizeof(unsigned long long) * want2);
         if (e != hipSuccess) {
             // (all or nothing: a half-made set would leave slots without buffers behind capacities that say otherwise)
             for (Slot& t : c->slots) { dfree(t.keys); dfree(t.keys2); }
+            dfree(kept);
             c->cap = 0; c->cap2 = 0;
             return fail(c, SPLAT_ERR_CAPACITY, std::string("cannot allocate pair buffer: ") + hipGetErrorString(e));
         }
     }
+    dfree(kept);                           // (a last slot beyond the slots in use: nothing to carry)
     c->cap = want; c->cap2 = want2;
     return SPLAT_OK;
 }

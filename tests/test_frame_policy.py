@@ -53,8 +53,7 @@ class Decision(C.Structure):
                 ("grid_long", C.c_uint32), ("pair_walk", C.c_int32), ("use_large_list", C.c_int32), ("layout_radius", C.c_int32), ("reserved", C.c_int32), ("next", State)]
 
 
-@pytest.fixture(scope="module")
-def L():
+def policy_lib():
     lib = C.CDLL(_lib.LIB_PATH)          # loads without a GPU
     lib.splat_policy_decide.restype = C.c_int
     lib.splat_policy_decide.argtypes = [C.POINTER(Knobs), C.POINTER(State), C.POINTER(Input), C.POINTER(Decision)]
@@ -63,6 +62,11 @@ def L():
     lib.splat_policy_struct_sizes.restype = None
     lib.splat_policy_struct_sizes.argtypes = [C.POINTER(C.c_uint64)]
     return lib
+
+
+@pytest.fixture(scope="module")
+def L():
+    return policy_lib()
 
 
 def test_header_symbols_are_exported_and_the_structs_are_the_librarys(L):
@@ -135,18 +139,27 @@ class Driver:
             self.step(angle)
         self.st.redo_armed = 0
 
-    def step(self, angle, report=None, awaited=0, idle=0, one_pass=1, has_keys2=1, focal=540.0):
-        """one frame at yaw `angle`; report = (overflow, redone) its scan will deliver (visible to the NEXT frames)"""
+    def step(self, angle, report=None, awaited=0, idle=0, one_pass=1, has_keys2=1, focal=540.0, cam=None):
+        """one frame at yaw `angle` -- or of `cam`, a splat_camera (the product's Camera.to_c) whose target is n_tiles tiles;
+        report = (overflow, redone) its scan will deliver (visible to the NEXT frames)"""
         self.frame += 1
         r = (self.frame - 1) % RING
         si = (self.frame - 1) % 4
         i = Input()
-        i.view[:] = list(yaw_view(angle))
-        i.proj[:] = list(PROJ)
-        i.w, i.h, i.htanx, i.htany, i.focal = 1920.0, 1080.0, 1.7778, 1.0, focal
-        i.cam[:] = [0.0, 0.0, 5.0]
-        i.lowpass = 0.01
-        i.tile_row0, i.n_tile_rows = 0, 68
+        if cam is None:
+            i.view[:] = list(yaw_view(angle))
+            i.proj[:] = list(PROJ)
+            i.w, i.h, i.htanx, i.htany, i.focal = 1920.0, 1080.0, 1.7778, 1.0, focal
+            i.cam[:] = [0.0, 0.0, 5.0]
+            i.lowpass = 0.01
+            i.tile_row0, i.n_tile_rows = 0, 68
+        else:
+            i.view[:] = list(cam.view)
+            i.proj[:] = list(cam.proj)
+            i.w, i.h, i.htanx, i.htany, i.focal = cam.w, cam.h, cam.htanx, cam.htany, cam.focal
+            i.cam[:] = list(cam.cam_pos)
+            i.lowpass = cam.lowpass
+            i.tile_row0, i.n_tile_rows = 0, (int(cam.h) + 15) // 16
         i.frame_idx, i.ring_entry, i.one_pass = self.frame, r, one_pass
         i.layout_valid, i.layout_cam = int(self.slots[si]["valid"]), self.slots[si]["cam"]
         i.awaited, i.idle, i.has_keys2, i.n_tiles = awaited, idle, has_keys2, self.n_tiles

@@ -8,7 +8,10 @@ was skipped on the device (then its image is untouched and splat_frames_dropped(
   THREE processes -- the default pipeline, SPLAT_PIPELINE=1 (one stream, nothing overlaps) and AMD_SERIALIZE_KERNEL=3 (the
   runtime waits before and after every launch) -- and the frames' digests are compared: a race between streams, or a fill the
   launches do not wait for (the allocation-time race of round 5 lived through two rounds), shows up as bytes that depend on
-  the schedule."""
+  the schedule.
+  --fresh-reference: also compare every fourth frame of a case (and its last) with the pose rendered by a NEW context that has
+  only that frame in its history -- the synchronous references above share the case's history (layouts, near-selection
+  thresholds, need_hint), so a history-driven bug that spoils both alike passes them."""
 import hashlib, json, os, subprocess
 import sys, time
 import numpy as np
@@ -94,6 +97,23 @@ def determinism(ncases, seed0):
     return bad
 
 
+fresh_reference = "--fresh-reference" in sys.argv
+if fresh_reference:
+    sys.argv.remove("--fresh-reference")
+
+
+def fresh_frame(g, p, H, W):
+    """the pose rendered synchronously by a context with nothing in its history but the scene"""
+    F = splat_amd.Renderer()
+    try:
+        F.upload(g)
+        out = np.zeros((H, W), np.uint32)
+        F.render_frame(p, out)
+    finally:
+        F.close()
+    return out
+
+
 if len(sys.argv) > 1 and sys.argv[1] == "--emit":
     emit(int(sys.argv[2])); sys.exit(0)
 if len(sys.argv) > 1 and sys.argv[1] == "--determinism":
@@ -141,6 +161,15 @@ for case in range(ncases):
                 bad += 1
                 print("CASE %d seed %d: frame %d differs from its synchronous render (%d px) and is not an untouched skip" % (case, seed0 + case, k, int((got[k] != ref).sum())))
     R.set_option(_lib.OPT_START_HINTS, hints)
+    if fresh_reference:
+        for k in sorted(set(range(0, len(poses), 4)) | {len(poses) - 1}):
+            ref = fresh_frame(g, poses[k], H, W)
+            if not np.array_equal(refs[k], ref):
+                bad += 1
+                print("CASE %d seed %d: frame %d rendered synchronously differs from a fresh context's (%d px)" % (case, seed0 + case, k, int((refs[k] != ref).sum())))
+            if not np.array_equal(got[k], ref) and not np.array_equal(got[k], garbage):
+                bad += 1
+                print("CASE %d seed %d: frame %d differs from a fresh context's (%d px) and is not an untouched skip" % (case, seed0 + case, k, int((got[k] != ref).sum())))
     if wrong > dropped:
         bad += 1
         print("CASE %d seed %d: %d frames untouched but only %d reported dropped" % (case, seed0 + case, wrong, dropped))
@@ -198,5 +227,5 @@ for case in range(ncases):
             bad += 1; print("CASE %d seed %d: streamed frame %d differs (%d px)" % (case, seed0 + case, k, int((outs[k] != ref).sum())))
     for im in imgs: R.device_free(im)
     R.close()
-print("fuzz_async: %d cases, %d failures, %d of %d asynchronous frames skipped on the device and reported, %.0f s" % (ncases, bad, tot_dropped, tot_frames, time.time() - t0))
+print("fuzz_async%s: %d cases, %d failures, %d of %d asynchronous frames skipped on the device and reported, %.0f s" % (" --fresh-reference" if fresh_reference else "", ncases, bad, tot_dropped, tot_frames, time.time() - t0))
 sys.exit(1 if bad else 0)
