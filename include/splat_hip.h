@@ -118,7 +118,10 @@ const char* splat_last_error(const splat_ctx* ctx);   /* ctx may be NULL: last c
 
 /* Scene upload: exactly GaussianList's buffers (src/gaussians.rs:408-416):
  * pos4 = positions.as_slice() (4n: x,y,z,1), cov3d = 3x3 column-major blocks (9n),
- * opacity (n), sh (48n, f_dc then f_rest un-transposed).  Host pointers; copied. */
+ * opacity (n), sh (48n, f_dc then f_rest un-transposed).  Host pointers; copied.
+ * Precondition of SPLAT_MODE_LIBM_EXP only: every opacity below 1 / (255 expf(-87)) ~ 2.4e35.  That mode's
+ * exponential stops falling at expf(-87) (splat_device_math.h, exp_libm), so a fragment whose exponent lies below -87
+ * is rejected like the reference's only while opacity * expf(-87) < 1/255.  Any float is accepted; nothing checks it. */
 int splat_upload_scene(splat_ctx* ctx, uint64_t n, const float* pos4, const float* cov3d,
                        const float* opacity, const float* sh);
 

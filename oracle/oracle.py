@@ -71,6 +71,9 @@ def lib():
         L.orc_fragment.argtypes = [fp, fp]
         L.orc_blend.argtypes = [C.c_uint32, fp]
         L.orc_blend.restype = C.c_uint32
+        L.orc_expf_n.argtypes = [C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int32]
+        L.orc_fragment_n.argtypes = [C.c_uint64, fp, fp, fp, fp, C.c_void_p, C.c_int32]
+        L.orc_blend_n.argtypes = [C.c_uint64, fp, fp, C.c_void_p, C.c_int32]
         L.orc_render.argtypes = [C.c_uint64, fp, fp, fp, fp, C.POINTER(Camera), C.POINTER(Conventions),
                                  C.POINTER(C.c_uint32), C.c_int32, C.c_int32, C.c_int32, C.POINTER(Stats)]
         L.orc_render.restype = C.c_int
@@ -154,6 +157,34 @@ def fragment(vdata9):
 def blend(old, frag4):
     f = np.ascontiguousarray(frag4, np.float32)
     return int(lib().orc_blend(int(old) & 0xFFFFFFFF, _fp(f)))
+
+
+def expf_n(first_bits=0, n=0, bits=None, nthreads=16):
+    """bits of glibc expf for the n floats whose bit patterns start at first_bits, or for the uint32 array `bits`"""
+    if bits is not None:
+        bits = np.ascontiguousarray(bits, np.uint32)
+        n = bits.size
+    out = np.empty(n, np.uint32)
+    lib().orc_expf_n(int(first_bits), bits.ctypes.data if bits is not None else None, n, out.ctypes.data, int(nthreads))
+    return out
+
+
+def fragment_n(sxy, ra, rb, nthreads=16):
+    """fragment() per tuple: sample sxy[n,2], record ra[n,4] = cx cy hx hy, rb[n,4] = A B C opacity -> (alpha[n], cov[n])"""
+    n = sxy.shape[0]
+    assert sxy.shape == (n, 2) and ra.shape == (n, 4) and rb.shape == (n, 4)
+    alpha, cov = np.empty(n, np.float32), np.empty(n, np.uint8)
+    lib().orc_fragment_n(n, _fp(sxy), _fp(ra), _fp(rb), _fp(alpha), cov.ctypes.data, int(nthreads))
+    return alpha, cov
+
+
+def blend_n(alpha, rgb, nthreads=16):
+    """blend() of fragment (rgb[i], alpha[i]) onto every state: uint32[n, 256] pixels (the state in R, G and B)"""
+    n = alpha.shape[0]
+    assert rgb.shape == (n, 3)
+    out = np.empty((n, 256), np.uint32)
+    lib().orc_blend_n(n, _fp(alpha), _fp(rgb), out.ctypes.data, int(nthreads))
+    return out
 
 
 def render(scene, cam, conv=None, argb=None, rows=None, nthreads=1):

@@ -246,6 +246,14 @@ double now_ms() {
     return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
 }
 
+template <class F> void orc_parallel(uint64_t n, int32_t nthreads, F f) {
+    nthreads = std::max(1, std::min(16, nthreads));
+    std::vector<std::thread> th;
+    for (int t = 0; t < nthreads; ++t)
+        th.emplace_back([=] { for (uint64_t i = n * t / nthreads, e = n * (t + 1) / nthreads; i < e; ++i) f(i); });
+    for (auto& x : th) x.join();
+}
+
 }  // namespace
 
 extern "C" {
@@ -356,6 +364,44 @@ void orc_fragment(const float v[9], float out[4]) {
 
 uint32_t orc_blend(uint32_t old_pixel, const float frag[4]) {
     return blend_px(old_pixel, frag[0], frag[1], frag[2], frag[3]);
+}
+
+// ---- array forms, for the per-function device tests (tests/test_gpu_device_math.py).  Plain loops over the
+// functions above and glibc, split over at most 16 threads; nothing here shares text with the kernels. ----
+// out[i] = expf(x_i), glibc; x_i = the float with bits first_bits + i when in_bits is NULL, else in_bits[i]
+void orc_expf_n(uint32_t first_bits, const uint32_t* in_bits, uint64_t n, uint32_t* out_bits, int32_t nthreads) {
+    orc_parallel(n, nthreads, [=](uint64_t i) {
+        uint32_t b = in_bits ? in_bits[i] : first_bits + (uint32_t)i;
+        float x; std::memcpy(&x, &b, 4);
+        float y = expf(x);
+        std::memcpy(out_bits + i, &y, 4);
+    });
+}
+
+// fragment() at sample (sx, sy) of the record with centre (cx, cy), half extents (hx, hy), conic (A, B, C) and
+// opacity, y up (the cross term carries the y-axis sign, as in the records K1 writes).  cov: the sample lies in the
+// record's rectangle (the rasteriser's test, orc_render); alpha: orc_fragment's, 0 where there is no fragment.
+void orc_fragment_n(uint64_t n, const float* sxy, const float* ra, const float* rb, float* out_alpha, uint8_t* out_cov,
+                    int32_t nthreads) {
+    orc_parallel(n, nthreads, [=](uint64_t i) {
+        const float dx = sxy[2 * i] - ra[4 * i], dy = ra[4 * i + 1] - sxy[2 * i + 1];
+        const bool cov = fabsf(dx) <= ra[4 * i + 2] && fabsf(dy) <= ra[4 * i + 3];
+        const float v[9] = {0.0f, 0.0f, 0.0f, rb[4 * i + 3], rb[4 * i], rb[4 * i + 1], rb[4 * i + 2], dx, dy};
+        float f[4];
+        orc_fragment(v, f);
+        out_cov[i] = cov ? 1 : 0;
+        out_alpha[i] = cov ? f[3] : 0.0f;
+    });
+}
+
+// blend() of the fragment (rgb_i, alpha_i) -- (0,0,0,0) when alpha_i == 0, as fragment() returns it -- onto every
+// state k = 0..255 (the same k in the three channels): out[i][k] = orc_blend(0x010101 * k, fragment)
+void orc_blend_n(uint64_t n, const float* alpha, const float* rgb, uint32_t* out, int32_t nthreads) {
+    orc_parallel(n, nthreads, [=](uint64_t i) {
+        float f[4] = {rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2], alpha[i]};
+        if (alpha[i] == 0.0f) f[0] = f[1] = f[2] = 0.0f;
+        for (uint32_t k = 0; k < 256; ++k) out[i * 256 + k] = orc_blend(k * 0x010101u, f);
+    });
 }
 
 int orc_render(uint64_t n, const float* pos4, const float* cov3d, const float* opacity, const float* sh48,

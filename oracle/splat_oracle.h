@@ -111,6 +111,14 @@ void orc_preprocess(uint64_t n, const float* pos4, const float* cov3d, const flo
 void orc_fragment(const float vdata[9], float out[4]);
 uint32_t orc_blend(uint32_t old_pixel, const float frag[4]);
 
+/* array forms for the per-function device tests: glibc expf over a range of bit patterns (in_bits NULL) or a list;
+ * fragment() with the rasteriser's rectangle test, records as K1 writes them (ra = cx cy hx hy, rb = A B C opacity,
+ * y up); blend() onto every state 0..255.  nthreads: at most 16 are used. */
+void orc_expf_n(uint32_t first_bits, const uint32_t* in_bits, uint64_t n, uint32_t* out_bits, int32_t nthreads);
+void orc_fragment_n(uint64_t n, const float* sxy, const float* ra, const float* rb, float* out_alpha, uint8_t* out_cov,
+                    int32_t nthreads);
+void orc_blend_n(uint64_t n, const float* alpha, const float* rgb, uint32_t* out, int32_t nthreads);
+
 /* ---- whole frame: render_to_buffer (src/pipelines.rs:66-86) ------------ */
 /* argb is in/out (the reference blends onto the caller's buffer), w*h u32
  * 0xAARRGGBB row-major.  Rows [row0,row1) only are touched (slab rendering);

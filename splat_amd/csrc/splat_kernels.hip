@@ -15,6 +15,26 @@
 #include <type_traits>
 
 #include "splat_internal.h"
+#include "splat_device_math.h"
+
+// exp_libm's table (splat_device_math.h holds the one the code uses), spelled out here as well: tests/test_host.py reads
+// the 32 entries from THIS file and checks them against 2^(i/32); the compiler checks that the two are the same list.
+namespace splat {
+static constexpr unsigned long long KERNELS_EXP2F_TAB[32] = {
+    0x3ff0000000000000ull, 0x3fefd9b0d3158574ull, 0x3fefb5586cf9890full, 0x3fef9301d0125b51ull, 0x3fef72b83c7d517bull,
+    0x3fef54873168b9aaull, 0x3fef387a6e756238ull, 0x3fef1e9df51fdee1ull, 0x3fef06fe0a31b715ull, 0x3feef1a7373aa9cbull,
+    0x3feedea64c123422ull, 0x3feece086061892dull, 0x3feebfdad5362a27ull, 0x3feeb42b569d4f82ull, 0x3feeab07dd485429ull,
+    0x3feea47eb03a5585ull, 0x3feea09e667f3bcdull, 0x3fee9f75e8ec5f74ull, 0x3feea11473eb0187ull, 0x3feea589994cce13ull,
+    0x3feeace5422aa0dbull, 0x3feeb737b0cdc5e5ull, 0x3feec49182a3f090ull, 0x3feed503b23e255dull, 0x3feee89f995ad3adull,
+    0x3feeff76f2fb5e47ull, 0x3fef199bdd85529cull, 0x3fef3720dcef9069ull, 0x3fef5818dcfba487ull, 0x3fef7c97337b9b5full,
+    0x3fefa4afa2a490daull, 0x3fefd0765b6e4540ull};
+constexpr bool exp2f_tab_is_the_headers() {
+    for (int i = 0; i < 32; ++i) if (KERNELS_EXP2F_TAB[i] != EXP2F_TAB_HOST[i]) return false;
+    return true;
+}
+static_assert(exp2f_tab_is_the_headers(), "splat_kernels.hip's copy of EXP2F_TAB differs from splat_device_math.h's");
+}  // namespace splat
+
 
 namespace splat {
 
@@ -979,8 +999,7 @@ __global__ __launch_bounds__(256) void preprocess_kernel(uint64_t n, const float
         for (int ch = 0; ch < 3; ++ch) col[ch] = col[ch] + 0.5f;   // HALF, no clamp
 
         // fragments with power < pthr have alpha < 1/255 for certain (margin 1e-3 >> f32 error)
-        float pthr = (opacity > 0.0f) ? (logf(1.0f / (255.0f * opacity)) - 1e-3f)
-                                      : ((opacity <= 0.0f) ? 3.0e38f : -3.0e38f);
+        float pthr = reject_threshold(opacity);
         // A colour that is not finite (SH coefficients of +-inf / NaN) is stored as the finite value that blends
         // to the same byte for every ACCEPTED fragment (alpha >= 1/255: +inf and FLT_MAX both saturate to 255,
         // -inf / NaN / -FLT_MAX all end at 0 through the saturating cast, src/pipelines.rs:159-161), so that a
@@ -2444,89 +2463,10 @@ __global__ __launch_bounds__(NT) void merge_runs_kernel(const unsigned int* __re
     merge(h, r2, h + r2, n - r2, g);                  // -> the list, sorted, back in place
 }
 
-// Does ANY sample s = lo + k (k = 0..count-1, all exactly representable) satisfy |s - c| <= h ?
-// |s - c| grows monotonically (also after f32 rounding) away from c, so testing the one or two
-// samples nearest to c is exact.
-__device__ __forceinline__ bool any_sample_covered(float c, float h, float lo, float hi, float off) {
-    float s1 = fminf(fmaxf(floorf(c - off) + off, lo), hi);
-    float s2 = fminf(s1 + 1.0f, hi);
-    return (int)(fabsf(s1 - c) <= h) | (int)(fabsf(s2 - c) <= h);
-}
-
 __device__ __forceinline__ unsigned long long uniform_u64(unsigned long long v) {
     // (readfirstlane returns int: go through unsigned, or the low word sign-extends)
     return ((unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |
            (unsigned long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)v);
-}
-
-// exp(x) for the compositor: the same reduction ocml's expf performs (2^(x*log2e) with a
-// compensated product, v_exp_f32 on the fractional part, ldexp) without its overflow/underflow
-// selects -- x is a Gaussian exponent, <= 0 and far above -100 wherever the result is used.
-__device__ __forceinline__ float exp_neg(float x) {
-    // x * log2(e) as an unevaluated sum ph + pl (compensated product); v_exp_f32 takes the rounded part
-    // whole -- it does its own range reduction and x is a Gaussian exponent (<= 0, far above -100
-    // wherever the result is used), so ocml's integer / fraction split, its ldexp and its range
-    // selects are not needed -- and the residual enters to first order: 2^(ph+pl) = 2^ph (1 + pl ln 2).
-    const float L2E_HI = __uint_as_float(0x3fb8aa3bu), L2E_LO = __uint_as_float(0x32a5705fu);
-    const float LN2 = 0.6931471805599453f;
-    float ph = x * L2E_HI;
-    float pl = fmaf(x, L2E_HI, -ph);
-    pl = fmaf(x, L2E_LO, pl);
-    const float e = __builtin_amdgcn_exp2f(ph);
-    return fmaf(e * pl, LN2, e);
-}
-
-// expf as glibc computes it (sysdeps/ieee754/flt-32/e_expf.c since 2.27: the ARM optimized-routines algorithm,
-// restated from its published description): x N/ln2 = k + r with N = 32, 2^(k/N) from a 32-entry table of doubles,
-// 2^(r/N) as a cubic, all in double, one rounding to float at the end.  Bit-identical to the host libm's expf --
-// which is what the oracle (and, through Rust's f32::exp, the reference on a glibc host) calls -- on every input
-// that can reach it here (checked against libm on random arguments by tests/test_host.py through the same
-// constants).  SPLAT_MODE_LIBM_EXP selects it: the frame is then the oracle's frame BIT FOR BIT, which shows that
-// the exponential's last place is the only thing the default build rounds differently.  It costs ~18 double
-// instructions per fragment, so it is a verification mode, not the default.
-__constant__ const unsigned long long EXP2F_TAB[32] = {      // tab[i] = bits(2^(i/32)) - (i << 47)
-    0x3ff0000000000000ull, 0x3fefd9b0d3158574ull, 0x3fefb5586cf9890full, 0x3fef9301d0125b51ull, 0x3fef72b83c7d517bull,
-    0x3fef54873168b9aaull, 0x3fef387a6e756238ull, 0x3fef1e9df51fdee1ull, 0x3fef06fe0a31b715ull, 0x3feef1a7373aa9cbull,
-    0x3feedea64c123422ull, 0x3feece086061892dull, 0x3feebfdad5362a27ull, 0x3feeb42b569d4f82ull, 0x3feeab07dd485429ull,
-    0x3feea47eb03a5585ull, 0x3feea09e667f3bcdull, 0x3fee9f75e8ec5f74ull, 0x3feea11473eb0187ull, 0x3feea589994cce13ull,
-    0x3feeace5422aa0dbull, 0x3feeb737b0cdc5e5ull, 0x3feec49182a3f090ull, 0x3feed503b23e255dull, 0x3feee89f995ad3adull,
-    0x3feeff76f2fb5e47ull, 0x3fef199bdd85529cull, 0x3fef3720dcef9069ull, 0x3fef5818dcfba487ull, 0x3fef7c97337b9b5full,
-    0x3fefa4afa2a490daull, 0x3fefd0765b6e4540ull};
-__device__ __forceinline__ float exp_libm(float x, const unsigned long long* __restrict__ tab /* LDS copy of EXP2F_TAB */) {
-    const double InvLn2N = 0x1.71547652b82fep+0 * 32.0, SHIFT = 0x1.8p+52;
-    const double C0 = 0x1.c6af84b912394p-5 / 32.0 / 32.0 / 32.0, C1 = 0x1.ebfce50fac4f3p-3 / 32.0 / 32.0, C2 = 0x1.62e42ff0c52d6p-1 / 32.0;
-    // below -87 expf is < 2e-38 and the fragment is rejected whatever its opacity; the clamp keeps k in the table's
-    // range without libm's underflow branches.  NaN stays NaN.
-    const double xd = (double)((x != x) ? x : fmaxf(x, -87.0f));
-    const double z = InvLn2N * xd;
-    double kd = z + SHIFT;                                     // round to nearest integer, in the low mantissa bits
-    const unsigned long long ki = (unsigned long long)__double_as_longlong(kd);
-    kd -= SHIFT;
-    const double r = z - kd;
-    const double sc = __longlong_as_double((long long)(tab[ki & 31ull] + (ki << 47)));
-    const double zz = C0 * r + C1;
-    const double r2 = r * r;
-    double y = C2 * r + 1.0;
-    y = zz * r2 + y;
-    y = y * sc;
-    return (float)y;
-}
-
-// k / 255.0f (IEEE) for every integer k in [0,255] in two instructions: 1/255 split into
-// hi + lo floats, fma(k, hi, k*lo) rounds once (checked exhaustively in tests/test_host.py).
-__device__ __forceinline__ float div255(float k) {
-    const float RH = 0x1.010102p-8f, RL = -0x1.fdfdfep-33f;
-    return fmaf(k, RH, k * RL);
-}
-// One channel of blend(): src/pipelines.rs:157-161.  Monotone non-decreasing in the state k for
-// fixed alpha/colour (every step -- /255, *ia, +const, *255, clamp, trunc -- is monotone under
-// round-to-nearest), which is what makes the [lo,hi] bracket of the early-out exact.
-// The u8 cast saturates (NaN/negative -> 0, >= 255 -> 255).  Clamping the blended value to [0,1]
-// BEFORE the *255 gives the same byte for every input (x in [0,1] is untouched; x > 1 -> 255; x < 0 or
-// NaN -> 0) and folds into the add as its clamp modifier: one VALU less per channel than med3.
-__device__ __forceinline__ float blend_channel(float k, float ia, float ac) {
-    const float x = __builtin_amdgcn_fmed3f(ia * div255(k) + ac, 0.0f, 1.0f);
-    return truncf(x * 255.0f);
 }
 
 struct WaveLds { float4 a[64]; float4 b[64]; float4 c[64]; };   // one batch of 64 records, private to a wave
@@ -2545,20 +2485,6 @@ struct WaveLds { float4 a[64]; float4 b[64]; float4 c[64]; };   // one batch of 
 // The batch is staged pair-interleaved, so that the operands are born in aligned register pairs (no moves):
 //   pair p (records 2p, 2p+1) = 24 floats:  cx0 cx1 cy0 cy1 | hx0 hx1 hy0 hy1 | A0 A1 C0 C1 | B0 B1 op0 op1 |
 //                                            r0 g0 r1 g1 | b0 - b1 -
-typedef float f2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f2 pk_add_clamp(f2 a, f2 b) {      // clamp(a + b, 0, 1) per component: the add's clamp modifier
-    f2 r;                                                      // (NaN -> 0 like the one-record loop's v_add_f32 ... clamp)
-    asm("v_pk_add_f32 %0, %1, %2 clamp" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-// blend() for two channels side by side: see blend_channel
-__device__ __forceinline__ f2 blend_channel2(f2 k, float ia, f2 ac) {
-    const float RH = 0x1.010102p-8f, RL = -0x1.fdfdfep-33f;
-    const f2 f = __builtin_elementwise_fma(k, (f2)(RH), k * RL);       // div255, both channels
-    const f2 y = pk_add_clamp(ia * f, ac) * 255.0f;
-    return (f2){truncf(y.x), truncf(y.y)};
-}
-
 // K4 -- compositor.  One wave = one 8x8 pixel block of a 16x16 tile (4 waves per workgroup, but
 // they never synchronise: each wave streams the tile's list through its own 3 KB of LDS, 64
 // records at a time, fetching the next batch into registers while it walks the current one).
@@ -2845,19 +2771,10 @@ __device__ __forceinline__ void composite_tile(unsigned char* smem, const unsign
         __builtin_amdgcn_wave_barrier();
         return kk;
     };
-    // fragment(): src/pipelines.rs:134-143, branch-free.  Returns alpha, forced to 0 where the
-    // fragment is rejected or the sample is not covered; `cov` reports coverage.
+    // fragment() is fragment_alpha (splat_device_math.h); the exponential it takes:
     auto expv = [&](float x) -> float {
         if constexpr (LIBM) return exp_libm(x, exptab);
         else return exp_neg(x);
-    };
-    auto frag_alpha = [&](const float4& a, const float4& b, auto e_of_power, bool& cov) -> float {
-        float dx = sxm - a.x, dy = a.y - sym;          // K1 folded the y-axis sign into b.y
-        cov = (fabsf(dx) <= a.z) & (fabsf(dy) <= a.w);
-        float power = -0.5f * (b.x * dx * dx + b.z * dy * dy) - b.y * dx * dy;
-        float alpha = fminf(0.99f, b.w * e_of_power(power));
-        bool accept = cov & !(power > 0.0f) & !(alpha < 1.0f / 255.0f);
-        return accept ? alpha : 0.0f;
     };
 
     bool need_far = false;                       // near selection: this wave's walk needs keys in front of the selection
@@ -2892,7 +2809,7 @@ __device__ __forceinline__ void composite_tile(unsigned char* smem, const unsign
                 const unsigned int jr = (jsel != 0xffffffffu) ? jsel : 0u;
                 const float4 a = L.a[jr], b = L.b[jr];
                 bool cov;
-                const float alpha = frag_alpha(a, b, expv, cov);      // exact, 0 when rejected
+                const float alpha = fragment_alpha(sxm, sym, a, b, expv, cov);      // exact, 0 when rejected
                 alast = (jsel != 0xffffffffu) ? alpha : alast;
             }
             if (__builtin_amdgcn_ballot_w64(!found) == 0ull || bs == lb) break;
@@ -2993,7 +2910,7 @@ __device__ __forceinline__ void composite_tile(unsigned char* smem, const unsign
     auto shade = [&](auto BRt, const float4& a, const float4& b, const float4& c) {
         constexpr bool BR = decltype(BRt)::value;
         bool cov;
-        const float alpha = frag_alpha(a, b, expv, cov);
+        const float alpha = fragment_alpha(sxm, sym, a, b, expv, cov);
         const float ia = 1.0f - alpha;
         const float ar = alpha * c.x, ag = alpha * c.y, ab = alpha * c.z;
         R = blend_channel(R, ia, ar);
@@ -3011,20 +2928,8 @@ __device__ __forceinline__ void composite_tile(unsigned char* smem, const unsign
                           const float4& q5) {
         constexpr bool BR = decltype(BRt)::value;
         const f2 cx = {q0.x, q0.y}, cy = {q0.z, q0.w}, A = {q2.x, q2.y}, C = {q2.z, q2.w}, Bc = {q3.x, q3.y}, op = {q3.z, q3.w};
-        const f2 dx = sxm2 - cx, dy = cy - sym2;                     // K1 folded the y-axis sign into the cross term
-        const bool cov0 = (fabsf(dx.x) <= q1.x) & (fabsf(dy.x) <= q1.z), cov1 = (fabsf(dx.y) <= q1.y) & (fabsf(dy.y) <= q1.w);
-        const f2 power = -0.5f * (A * dx * dx + C * dy * dy) - Bc * dx * dy;
-        // exp_neg, both records
-        const float L2E_HI = __uint_as_float(0x3fb8aa3bu), L2E_LO = __uint_as_float(0x32a5705fu), LN2 = 0.6931471805599453f;
-        const f2 ph = power * L2E_HI;
-        f2 pl = __builtin_elementwise_fma(power, (f2)(L2E_HI), -ph);
-        pl = __builtin_elementwise_fma(power, (f2)(L2E_LO), pl);
-        const f2 e = {__builtin_amdgcn_exp2f(ph.x), __builtin_amdgcn_exp2f(ph.y)};
-        const f2 ex = __builtin_elementwise_fma(e * pl, (f2)(LN2), e);
-        const f2 al = op * ex;
-        const float a0 = fminf(0.99f, al.x), a1 = fminf(0.99f, al.y);
-        const float alpha0 = (cov0 & !(power.x > 0.0f) & !(a0 < 1.0f / 255.0f)) ? a0 : 0.0f;
-        const float alpha1 = (cov1 & !(power.y > 0.0f) & !(a1 < 1.0f / 255.0f)) ? a1 : 0.0f;
+        const f2 alpha = fragment_alpha2(sxm2, sym2, cx, cy, q1, A, C, Bc, op);
+        const float alpha0 = alpha.x, alpha1 = alpha.y;
         auto blend_one = [&](float alpha, f2 rg, float b) {
             const float ia = 1.0f - alpha;
             const f2 arg = alpha * rg;
