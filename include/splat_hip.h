@@ -36,7 +36,7 @@ extern "C" {
  * with: a binding compiled against another header (splat_stats grew by two fields between versions 4 and 5; a caller that
  * passes the shorter struct has 16 bytes written past it) compares the two before its first call -- the ctypes binding,
  * rust/src/pipelines_hip.rs and the C++ host mirror all do -- and splat_stats_size() tells the byte count it will write. */
-#define SPLAT_ABI_VERSION 6
+#define SPLAT_ABI_VERSION 7
 
 /* modes: bit flags, 0 = the default */
 #define SPLAT_MODE_EXACT 0       /* back-to-front, 8-bit truncation per splat as blend() does it; the exponential of
@@ -129,6 +129,22 @@ int splat_upload_scene(splat_ctx* ctx, uint64_t n, const float* pos4, const floa
  * rot4 (4n, nalgebra coords order i,j,k,w, un-normalised), cov3d_out (9n).  Host pointers. */
 int splat_compute_cov3d(splat_ctx* ctx, uint64_t n, const float* scales3, const float* rot4,
                         float* cov3d_out);
+
+/* The buffers of splat_upload_scene, but in DEVICE memory of the context's GPU (same layouts: pos4 4n, cov3d 9n
+ * col-major blocks, opacity n, sh 48n).  producer_stream: the hipStream_t the caller's work that wrote them was
+ * enqueued on (NULL = the caller has already synchronised); the library orders itself behind it with an event.
+ * Synchronous like splat_upload_scene: on return the inputs may be freed or overwritten.  Nothing of the scene
+ * crosses PCIe: the Morton order, the block bounds and the packing are computed on the GPU, with the results of
+ * splat_upload_scene bit for bit (every frame afterwards is the same frame). */
+int splat_upload_scene_device(splat_ctx* ctx, uint64_t n, const void* d_pos4, const void* d_cov3d,
+                              const void* d_opacity, const void* d_sh, void* producer_stream);
+/* compute_cov3d with device in, device out (no copies); producer_stream as above.  Returns when d_cov3d_out is written. */
+int splat_compute_cov3d_device(splat_ctx* ctx, uint64_t n, const void* d_scales3, const void* d_rot4,
+                               void* d_cov3d_out, void* producer_stream);
+/* Debug / stage parity: the stored scene order and K1 block bounds of the current scene.
+ * orig_out: n u32 (slot j holds original Gaussian orig[j]); bounds_out: ceil(n/256) x 8 f32
+ * (lo[3], hi[3], fmax, pad), either may be NULL.  n and n_blocks must be the scene's. */
+int splat_get_scene_layout(splat_ctx* ctx, uint32_t* orig_out, uint64_t n, float* bounds_out, uint64_t n_blocks);
 
 /* Restrict rendering to tile rows [tile_row0, tile_row1) (multi-GPU slabs); (0,-1) = all. */
 int splat_set_slab(splat_ctx* ctx, int32_t tile_row0, int32_t tile_row1);

@@ -39,7 +39,7 @@ pub const SPLAT_OPT_LARGE_SPLAT_TILES: i32 = 22;
 pub const SPLAT_OPT_LARGE_LIST_MIN: i32 = 23;
 pub const SPLAT_OPT_START_REFINE: i32 = 24;
 /// SPLAT_ABI_VERSION of the header this file mirrors; compared with splat_abi_version() before the first call
-pub const SPLAT_ABI_VERSION: u32 = 6;
+pub const SPLAT_ABI_VERSION: u32 = 7;
 
 #[repr(C)] pub struct SplatCtx { _private: [u8; 0] }
 #[repr(C)] pub struct SplatMulti { _private: [u8; 0] }
@@ -88,6 +88,13 @@ extern "C" {
                               opacity: *const f32, sh: *const f32) -> c_int;
     pub fn splat_compute_cov3d(ctx: *mut SplatCtx, n: u64, scales3: *const f32, rot4: *const f32,
                                cov3d_out: *mut f32) -> c_int;
+    // the scene from DEVICE buffers of the context's GPU (same layouts); producer_stream: the hipStream_t that wrote them, or null
+    pub fn splat_upload_scene_device(ctx: *mut SplatCtx, n: u64, d_pos4: *const c_void, d_cov3d: *const c_void,
+                                     d_opacity: *const c_void, d_sh: *const c_void, producer_stream: *mut c_void) -> c_int;
+    pub fn splat_compute_cov3d_device(ctx: *mut SplatCtx, n: u64, d_scales3: *const c_void, d_rot4: *const c_void,
+                                      d_cov3d_out: *mut c_void, producer_stream: *mut c_void) -> c_int;
+    // debug / stage parity: the stored order (n u32) and the K1 block bounds (ceil(n/256) x 8 f32); either may be null
+    pub fn splat_get_scene_layout(ctx: *mut SplatCtx, orig_out: *mut u32, n: u64, bounds_out: *mut f32, n_blocks: u64) -> c_int;
     pub fn splat_set_slab(ctx: *mut SplatCtx, tile_row0: i32, tile_row1: i32) -> c_int;
     pub fn splat_tile_row_loads(ctx: *mut SplatCtx, cam: *const SplatCamera, row_pairs: *mut u64, n_rows: i32) -> c_int;
     pub fn splat_render(ctx: *mut SplatCtx, cam: *const SplatCamera, argb: *mut u32, stats: *mut SplatStats) -> c_int;

@@ -52,6 +52,9 @@ SYMBOLS = [
     ("splat_last_error", C.c_char_p, [C.c_void_p]),
     ("splat_upload_scene", C.c_int, [C.c_void_p, C.c_uint64, _fp, _fp, _fp, _fp]),
     ("splat_compute_cov3d", C.c_int, [C.c_void_p, C.c_uint64, _fp, _fp, _fp]),
+    ("splat_upload_scene_device", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("splat_compute_cov3d_device", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("splat_get_scene_layout", C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint64, _fp, C.c_uint64]),
     ("splat_set_slab", C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     ("splat_tile_row_loads", C.c_int, [C.c_void_p, C.POINTER(CameraC), C.POINTER(C.c_uint64), C.c_int32]),
     ("splat_render", C.c_int, [C.c_void_p, C.POINTER(CameraC), C.POINTER(C.c_uint32), C.POINTER(Stats)]),
@@ -129,7 +132,7 @@ OPT_COUNT_FIRST = 21
 OPT_LARGE_SPLAT_TILES = 22
 OPT_LARGE_LIST_MIN = 23
 OPT_START_REFINE = 24
-ABI_VERSION = 6          # SPLAT_ABI_VERSION of the header these structures were written against
+ABI_VERSION = 7          # SPLAT_ABI_VERSION of the header these structures were written against
 
 _LIB = None
 

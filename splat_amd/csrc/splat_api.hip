@@ -92,7 +92,8 @@ struct splat_ctx {
     unsigned int* orig = nullptr;          // slot -> original Gaussian index (Morton order of position)
     BlockBounds* bounds = nullptr;         // per K1 block of 256 slots (block culling)
     bool cull_blocks = true;               // SPLAT_CULL=0 disables
-    std::vector<unsigned int> h_orig;
+    std::vector<unsigned int> h_orig;      // host copy of orig (ensure_h_orig: a device upload leaves it empty until a debug getter asks)
+    float upload_sort_ms = 0.0f;           // device time of the sort inside the most recent splat_upload_scene_device
     // per-frame buffers
     Slot slots[N_SLOTS];
     unsigned int m_alloc = 0;
@@ -1505,57 +1506,41 @@ int splat_set_stream(splat_ctx* c, void* stream) {
     return rc;
 }
 
-int splat_upload_scene(splat_ctx* c, uint64_t n, const float* pos4, const float* cov3d, const float* opacity,
-                       const float* sh) {
-    if (!c) return SPLAT_ERR_INVALID;
-    if (n && (!pos4 || !cov3d || !opacity || !sh)) return fail(c, SPLAT_ERR_INVALID, "NULL scene pointer");
-    if (n >= 0xFFFFFFFFull) return fail(c, SPLAT_ERR_INVALID, "too many Gaussians (index is 32-bit)");
+}  // extern "C"
+
+namespace {
+// The two scene uploads (host buffers, device buffers) share everything but how the order, the bounds and the planes get
+// their values.  upload_begin: the frames of the scene being replaced end, the old scene goes.
+int upload_begin(splat_ctx* c) {
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     (void)finish_frame(c);          // (frames of the scene being replaced: nothing left to redo)
     c->deferred_drop = false; c->frames_drop_reported = c->frames_dropped;
     int rc = sync_all(c);
     if (rc != SPLAT_OK) return rc;
     free_scene(c);
-    if (n == 0) return SPLAT_OK;
-    morton_order(n, pos4, c->h_orig);
-    float *d_pos = nullptr, *d_cov = nullptr, *d_op = nullptr, *d_sh = nullptr;
-    auto cleanup = [&] { dfree(d_pos); dfree(d_cov); dfree(d_op); dfree(d_sh); };
+    return SPLAT_OK;
+}
+// ... the buffers that live as long as the scene (the bounds apart: the host path makes them once it has their values)
+hipError_t alloc_scene(splat_ctx* c, uint64_t n) {
     hipError_t e;
-#define UP_TRY(expr)                                                            \
-    if ((e = (expr)) != hipSuccess) {                                            \
-        cleanup();                                                               \
-        return fail(c, SPLAT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e)); \
-    }
-    UP_TRY(dmalloc(c, &c->planes, sizeof(float4) * SCENE_PLANES * n));
-    UP_TRY(dmalloc(c, &c->orig, sizeof(unsigned int) * n));
+#define AS_TRY(expr) if ((e = (expr)) != hipSuccess) return e
+    AS_TRY(dmalloc(c, &c->planes, sizeof(float4) * SCENE_PLANES * n));
+    AS_TRY(dmalloc(c, &c->orig, sizeof(unsigned int) * n));
     for (Slot& s : c->slots) {
-        UP_TRY(dmalloc(c, &s.recs, sizeof(Rec) * n));
-        UP_TRY(dmalloc(c, &s.blockinfo, sizeof(unsigned int) * ((n + 255) / 256)));
-        UP_TRY(hipMemsetAsync(s.blockinfo, 0, sizeof(unsigned int) * ((n + 255) / 256), c->stream));
+        AS_TRY(dmalloc(c, &s.recs, sizeof(Rec) * n));
+        AS_TRY(dmalloc(c, &s.blockinfo, sizeof(unsigned int) * ((n + 255) / 256)));
+        AS_TRY(hipMemsetAsync(s.blockinfo, 0, sizeof(unsigned int) * ((n + 255) / 256), c->stream));
         if (c->large_tiles >= 0) {          // (SPLAT_LARGE_TILES < 0: no list, K1's blocks expand their close-ups themselves)
-            UP_TRY(dmalloc(c, &s.large_list, sizeof(uint4) * n));
-            UP_TRY(dmalloc(c, &s.large_count, sizeof(unsigned int) * 4));
-            UP_TRY(hipMemsetAsync(s.large_count, 0, sizeof(unsigned int) * 4, c->stream));
+            AS_TRY(dmalloc(c, &s.large_list, sizeof(uint4) * n));
+            AS_TRY(dmalloc(c, &s.large_count, sizeof(unsigned int) * 4));
+            AS_TRY(hipMemsetAsync(s.large_count, 0, sizeof(unsigned int) * 4, c->stream));
         }
     }
-    UP_TRY(hipMemcpyAsync(c->orig, c->h_orig.data(), sizeof(unsigned int) * n, hipMemcpyHostToDevice, c->stream));
-    std::vector<BlockBounds> hb;
-    block_bounds(n, pos4, cov3d, c->h_orig, hb);
-    UP_TRY(dmalloc(c, &c->bounds, sizeof(BlockBounds) * hb.size()));
-    UP_TRY(hipMemcpyAsync(c->bounds, hb.data(), sizeof(BlockBounds) * hb.size(), hipMemcpyHostToDevice, c->stream));
-    UP_TRY(dmalloc(c, &d_pos, sizeof(float) * 4 * n));
-    UP_TRY(dmalloc(c, &d_cov, sizeof(float) * 9 * n));
-    UP_TRY(dmalloc(c, &d_op, sizeof(float) * n));
-    UP_TRY(dmalloc(c, &d_sh, sizeof(float) * 48 * n));
-    UP_TRY(hipMemcpyAsync(d_pos, pos4, sizeof(float) * 4 * n, hipMemcpyHostToDevice, c->stream));
-    UP_TRY(hipMemcpyAsync(d_cov, cov3d, sizeof(float) * 9 * n, hipMemcpyHostToDevice, c->stream));
-    UP_TRY(hipMemcpyAsync(d_op, opacity, sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
-    UP_TRY(hipMemcpyAsync(d_sh, sh, sizeof(float) * 48 * n, hipMemcpyHostToDevice, c->stream));
-    launch_pack_scene(c->stream, n, d_pos, d_cov, d_op, d_sh, c->orig, c->planes);
-    UP_TRY(hipGetLastError());
-    UP_TRY(hipStreamSynchronize(c->stream));
-#undef UP_TRY
-    cleanup();
+#undef AS_TRY
+    return hipSuccess;
+}
+// ... and what follows the packing: the context's per-scene state starts over, the per-tile arrays and key buffers exist
+void upload_finish(splat_ctx* c, uint64_t n) {
     c->n = n;
     c->region_mult = 0;
     c->bucket_failed = false;              // key storage is sized at the first frame (prepare_binning)
@@ -1574,6 +1559,125 @@ int splat_upload_scene(splat_ctx* c, uint64_t n, const float* pos4, const float*
         const uint64_t want2 = std::min<uint64_t>(std::max<uint64_t>(c->cap2, default_keys2_capacity(c)), KEY_ENTRIES_MAX);
         if ((want + want2) * 8ull * (uint64_t)slots_in_use(c) <= c->bucket_bytes && ensure_keys(c, want, want2) != SPLAT_OK) (void)hipGetLastError();
     }
+}
+// The host copy of the scene's order (the debug getters translate slots with it): the host upload leaves it behind, a
+// device upload does not -- it is fetched when first asked for.
+int ensure_h_orig(splat_ctx* c) {
+    if (c->h_orig.size() == c->n) return SPLAT_OK;
+    std::vector<unsigned int> h(c->n);
+    if (c->n) HIP_TRY(c, hipMemcpy(h.data(), c->orig, sizeof(unsigned int) * c->n, hipMemcpyDeviceToHost));
+    c->h_orig.swap(h);
+    return SPLAT_OK;
+}
+// Work the caller enqueued on `producer` comes first: the context's stream waits for an event recorded there.
+hipError_t follow_producer(splat_ctx* c, void* producer) {
+    if (!producer) return hipSuccess;          // (the caller has synchronised)
+    hipEvent_t ev = nullptr;
+    hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    if (e != hipSuccess) return e;
+    e = hipEventRecord(ev, (hipStream_t)producer);
+    if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, ev, 0);
+    (void)hipEventDestroy(ev);                 // (released once the wait has been satisfied)
+    return e;
+}
+}  // namespace
+
+extern "C" {
+
+int splat_upload_scene(splat_ctx* c, uint64_t n, const float* pos4, const float* cov3d, const float* opacity,
+                       const float* sh) {
+    if (!c) return SPLAT_ERR_INVALID;
+    if (n && (!pos4 || !cov3d || !opacity || !sh)) return fail(c, SPLAT_ERR_INVALID, "NULL scene pointer");
+    if (n >= 0xFFFFFFFFull) return fail(c, SPLAT_ERR_INVALID, "too many Gaussians (index is 32-bit)");
+    int rc = upload_begin(c);
+    if (rc != SPLAT_OK) return rc;
+    if (n == 0) return SPLAT_OK;
+    morton_order(n, pos4, c->h_orig);
+    float *d_pos = nullptr, *d_cov = nullptr, *d_op = nullptr, *d_sh = nullptr;
+    auto cleanup = [&] { dfree(d_pos); dfree(d_cov); dfree(d_op); dfree(d_sh); };
+    hipError_t e;
+#define UP_TRY(expr)                                                            \
+    if ((e = (expr)) != hipSuccess) {                                            \
+        cleanup();                                                               \
+        return fail(c, SPLAT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e)); \
+    }
+    UP_TRY(alloc_scene(c, n));
+    UP_TRY(hipMemcpyAsync(c->orig, c->h_orig.data(), sizeof(unsigned int) * n, hipMemcpyHostToDevice, c->stream));
+    std::vector<BlockBounds> hb;
+    block_bounds(n, pos4, cov3d, c->h_orig, hb);
+    UP_TRY(dmalloc(c, &c->bounds, sizeof(BlockBounds) * hb.size()));
+    UP_TRY(hipMemcpyAsync(c->bounds, hb.data(), sizeof(BlockBounds) * hb.size(), hipMemcpyHostToDevice, c->stream));
+    UP_TRY(dmalloc(c, &d_pos, sizeof(float) * 4 * n));
+    UP_TRY(dmalloc(c, &d_cov, sizeof(float) * 9 * n));
+    UP_TRY(dmalloc(c, &d_op, sizeof(float) * n));
+    UP_TRY(dmalloc(c, &d_sh, sizeof(float) * 48 * n));
+    UP_TRY(hipMemcpyAsync(d_pos, pos4, sizeof(float) * 4 * n, hipMemcpyHostToDevice, c->stream));
+    UP_TRY(hipMemcpyAsync(d_cov, cov3d, sizeof(float) * 9 * n, hipMemcpyHostToDevice, c->stream));
+    UP_TRY(hipMemcpyAsync(d_op, opacity, sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
+    UP_TRY(hipMemcpyAsync(d_sh, sh, sizeof(float) * 48 * n, hipMemcpyHostToDevice, c->stream));
+    launch_pack_scene(c->stream, n, d_pos, d_cov, d_op, d_sh, c->orig, c->planes);
+    UP_TRY(hipGetLastError());
+    UP_TRY(hipStreamSynchronize(c->stream));
+#undef UP_TRY
+    cleanup();
+    upload_finish(c, n);
+    return SPLAT_OK;
+}
+
+int splat_upload_scene_device(splat_ctx* c, uint64_t n, const void* d_pos4, const void* d_cov3d, const void* d_opacity,
+                              const void* d_sh, void* producer_stream) {
+    if (!c) return SPLAT_ERR_INVALID;
+    if (n && (!d_pos4 || !d_cov3d || !d_opacity || !d_sh)) return fail(c, SPLAT_ERR_INVALID, "NULL scene pointer");
+    if (n >= 0xFFFFFFFFull) return fail(c, SPLAT_ERR_INVALID, "too many Gaussians (index is 32-bit)");
+    int rc = upload_begin(c);
+    if (rc != SPLAT_OK) return rc;
+    if (n == 0) return SPLAT_OK;
+    const float *pos4 = (const float*)d_pos4, *cov3d = (const float*)d_cov3d;
+    // the sort's ping-pong arrays (16 B per Gaussian) and its scan tables: all that exists beside the scene itself
+    uint32_t* d_sort = nullptr; unsigned char* d_small = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    auto cleanup = [&] { dfree(d_sort); dfree(d_small); for (hipEvent_t& x : ev) if (x) { (void)hipEventDestroy(x); x = nullptr; } };
+    hipError_t e;
+#define UP_TRY(expr)                                                            \
+    if ((e = (expr)) != hipSuccess) {                                            \
+        cleanup();                                                               \
+        return fail(c, SPLAT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e)); \
+    }
+    UP_TRY(alloc_scene(c, n));
+    UP_TRY(dmalloc(c, &c->bounds, sizeof(BlockBounds) * ((n + 255) / 256)));
+    UP_TRY(dmalloc(c, &d_sort, sizeof(uint32_t) * 4 * n));
+    UP_TRY(dmalloc(c, &d_small, scene_order_small_bytes(n)));
+    UP_TRY(hipEventCreate(&ev[0]));
+    UP_TRY(hipEventCreate(&ev[1]));
+    UP_TRY(follow_producer(c, producer_stream));
+    launch_scene_order(c->stream, n, pos4, d_sort, d_small, c->orig, ev[0], ev[1]);
+    launch_block_bounds(c->stream, n, pos4, cov3d, c->orig, c->bounds);
+    launch_pack_scene(c->stream, n, pos4, cov3d, (const float*)d_opacity, (const float*)d_sh, c->orig, c->planes);
+    UP_TRY(hipGetLastError());
+    UP_TRY(hipStreamSynchronize(c->stream));
+#undef UP_TRY
+    c->upload_sort_ms = 0.0f;
+    (void)hipEventElapsedTime(&c->upload_sort_ms, ev[0], ev[1]);
+    cleanup();
+    upload_finish(c, n);
+    return SPLAT_OK;
+}
+
+// (debug, not part of the ABI)  Device time of the sort inside the most recent splat_upload_scene_device, in milliseconds.
+int splat_debug_upload_sort_ms(splat_ctx* c, double* ms) {
+    if (!c || !ms) return SPLAT_ERR_INVALID;
+    *ms = c->upload_sort_ms;
+    return SPLAT_OK;
+}
+
+int splat_get_scene_layout(splat_ctx* c, uint32_t* orig_out, uint64_t n, float* bounds_out, uint64_t n_blocks) {
+    if (!c) return SPLAT_ERR_INVALID;
+    if (n != c->n || n_blocks != (c->n + 255) / 256) return fail(c, SPLAT_ERR_INVALID, "scene layout size mismatch");
+    if (n == 0) return SPLAT_OK;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    static_assert(sizeof(BlockBounds) == 8 * sizeof(float), "bounds_out is 8 floats per block");
+    if (orig_out) HIP_TRY(c, hipMemcpy(orig_out, c->orig, sizeof(unsigned int) * n, hipMemcpyDeviceToHost));
+    if (bounds_out) HIP_TRY(c, hipMemcpy(bounds_out, c->bounds, sizeof(BlockBounds) * n_blocks, hipMemcpyDeviceToHost));
     return SPLAT_OK;
 }
 
@@ -1599,6 +1703,22 @@ int splat_compute_cov3d(splat_ctx* c, uint64_t n, const float* scales3, const fl
     if (e != hipSuccess) rc = fail(c, SPLAT_ERR_HIP, std::string("splat_compute_cov3d: ") + hipGetErrorString(e));
     dfree(d_s); dfree(d_r); dfree(d_o);
     return rc;
+}
+
+int splat_compute_cov3d_device(splat_ctx* c, uint64_t n, const void* d_scales3, const void* d_rot4, void* d_cov3d_out,
+                               void* producer_stream) {
+    if (!c) return SPLAT_ERR_INVALID;
+    if (n == 0) return SPLAT_OK;
+    if (!d_scales3 || !d_rot4 || !d_cov3d_out) return fail(c, SPLAT_ERR_INVALID, "NULL pointer");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipError_t e = follow_producer(c, producer_stream);
+    if (e == hipSuccess) {
+        launch_cov3d(c->stream, n, (const float*)d_scales3, (const float*)d_rot4, (float*)d_cov3d_out);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return fail(c, SPLAT_ERR_HIP, std::string("splat_compute_cov3d_device: ") + hipGetErrorString(e));
+    return SPLAT_OK;
 }
 
 int splat_set_slab(splat_ctx* c, int32_t tile_row0, int32_t tile_row1) {
@@ -1993,6 +2113,8 @@ int splat_get_records(splat_ctx* c, splat_record* out, uint64_t n) {
     }
     HIP_TRY(c, hipMemcpy(d.data(), s.depth, sizeof(float) * n, hipMemcpyDeviceToHost));
     HIP_TRY(c, hipMemcpy(q.data(), s.rect, sizeof(ushort4) * n, hipMemcpyDeviceToHost));
+    rc = ensure_h_orig(c);
+    if (rc != SPLAT_OK) return rc;
     for (uint64_t j = 0; j < n; ++j) {          // everything lives in slot order; the caller gets original order
         const uint64_t i = c->h_orig[j];
         splat_record& o = out[i];
@@ -2079,6 +2201,8 @@ int splat_get_tile_lists(splat_ctx* c, uint32_t* tile_offsets, uint64_t n_offset
                     HIP_TRY(c, hipMemcpy(k.data() + tile_offsets[t], s.keys + beg[t], sizeof(unsigned long long) * len[t],
                                          hipMemcpyDeviceToHost));
         }
+        rc = ensure_h_orig(c);
+        if (rc != SPLAT_OK) return rc;
         for (uint64_t i = 0; i < n_order; ++i) order[i] = c->h_orig[(uint32_t)k[i]];      // keys carry slots
     }
     return SPLAT_OK;

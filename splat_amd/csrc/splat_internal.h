@@ -121,6 +121,15 @@ void use_launch_knobs(const LaunchKnobs* k);
 void launch_pack_scene(hipStream_t s, uint64_t n, const float* pos4, const float* cov3d, const float* opacity,
                        const float* sh, const unsigned int* perm, float4* planes);
 void launch_cov3d(hipStream_t s, uint64_t n, const float* scales3, const float* rot4, float* cov3d);
+struct BlockBounds;
+// The scene's order on the device (splat_upload_scene_device): orig[j] = the Gaussian stored in slot j, as morton_order of
+// splat_api.hip orders them.  pingpong: 4 n words (the sort's two key and two index arrays); small:
+// scene_order_small_bytes(n) bytes (scan tables, partial boxes).  The two events, when given, are recorded around the sort.
+size_t scene_order_small_bytes(uint64_t n);
+void launch_scene_order(hipStream_t s, uint64_t n, const float* pos4, uint32_t* pingpong, void* small, unsigned int* orig,
+                        hipEvent_t sort_begin = nullptr, hipEvent_t sort_end = nullptr);
+// ... and the bounds of its K1 blocks, as block_bounds of splat_api.hip computes them
+void launch_block_bounds(hipStream_t s, uint64_t n, const float* pos4, const float* cov3d, const unsigned int* orig, BlockBounds* bounds);
 void launch_preprocess(hipStream_t s, uint64_t n, const float4* planes, const unsigned int* orig, FrameConst fc, Rec* recs,
                        float* depth, ushort4* rect, unsigned int* counts, unsigned int* vislist, unsigned long long* keys,
                        const BlockBounds* bounds,

@@ -162,6 +162,271 @@ __global__ __launch_bounds__(256) void cov3d_kernel(uint64_t n, const float* __r
     for (int e = 0; e < 9; ++e) out[9 * t + e] = cov.m[e];
 }
 
+// ---------------------------------------------------------------------------
+// Scene order and block bounds on the device (splat_upload_scene_device).  morton_order and block_bounds of
+// splat_api.hip are the specification: the same f32 arithmetic, the same order among equal codes, the same bits in the
+// bounds -- a frame after a device upload is the frame after a host upload of the same data.
+//   scene_box_kernel / scene_box_final_kernel   per-axis min / max of the finite coordinates, then lo and 1023 / (hi - lo)
+//   morton_code_kernel                          the 30-bit code of every Gaussian
+//   radix_hist_kernel, radix_scan_kernel, radix_scatter_kernel   one 8-bit pass of a stable LSD radix sort of (code, index):
+//       per-workgroup digit counts, an exclusive scan along every digit's row of the (digit, workgroup) table, and a
+//       scatter that ranks by wave ballots and LDS prefix sums -- never by the arrival order of an atomic, so the
+//       order is the same run to run, and equal codes stay in index order (std::sort of (code << 32) | index)
+//   block_bounds_kernel                         one workgroup per 256 consecutive slots
+// ---------------------------------------------------------------------------
+constexpr int SORT_ITEMS = 16;                       // keys per thread of a sort tile
+constexpr int SORT_TILE = 256 * SORT_ITEMS;          // keys per workgroup: the (digit, workgroup) table is n / 16 words
+constexpr unsigned int BOX_GROUPS_MAX = 1024;        // partial boxes of the first reduction
+
+__device__ __forceinline__ uint32_t spread3_dev(uint32_t v) {
+    v &= 0x3ffu;
+    v = (v | (v << 16)) & 0x030000ffu;
+    v = (v | (v << 8)) & 0x0300f00fu;
+    v = (v | (v << 4)) & 0x030c30c3u;
+    v = (v | (v << 2)) & 0x09249249u;
+    return v;
+}
+// std::min(a, b) / std::max(a, b) as the host evaluates them, `a` the value seen earlier: the EARLIER of two equal values
+// is kept (+0 and -0 compare equal and differ in the bounds' bits)
+__device__ __forceinline__ float min_keep_first(float a, float b) { return (b < a) ? b : a; }
+__device__ __forceinline__ float max_keep_first(float a, float b) { return (a < b) ? b : a; }
+
+// partial[g][0..2] = min, [4..6] = max over the finite coordinates workgroup g saw (+inf / -inf where it saw none)
+__global__ __launch_bounds__(256) void scene_box_kernel(uint64_t n, const float* __restrict__ pos4, float* __restrict__ partial) {
+    __shared__ float red[4][6];
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256u)
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const float v = pos4[4 * i + a];
+            if (finitef(v)) { lo[a] = min_keep_first(lo[a], v); hi[a] = max_keep_first(hi[a], v); }
+        }
+#pragma unroll
+    for (int k = 32; k >= 1; k >>= 1)
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = min_keep_first(lo[a], __shfl_xor(lo[a], k));
+            hi[a] = max_keep_first(hi[a], __shfl_xor(hi[a], k));
+        }
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0)
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { red[w][a] = lo[a]; red[w][3 + a] = hi[a]; }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const int a = threadIdx.x;
+        float l = red[0][a], h = red[0][3 + a];
+        for (int k = 1; k < 4; ++k) { l = min_keep_first(l, red[k][a]); h = max_keep_first(h, red[k][3 + a]); }
+        partial[8 * (uint64_t)blockIdx.x + a] = l;
+        partial[8 * (uint64_t)blockIdx.x + 4 + a] = h;
+    }
+}
+// box[0..2] = lo, box[4..6] = sc of morton_order (one float divide per axis, 0 where the axis has no extent)
+__global__ __launch_bounds__(256) void scene_box_final_kernel(unsigned int groups, const float* __restrict__ partial, float* __restrict__ box) {
+    __shared__ float red[4][6];
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (unsigned int g = threadIdx.x; g < groups; g += 256u)
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = min_keep_first(lo[a], partial[8 * (uint64_t)g + a]);
+            hi[a] = max_keep_first(hi[a], partial[8 * (uint64_t)g + 4 + a]);
+        }
+#pragma unroll
+    for (int k = 32; k >= 1; k >>= 1)
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = min_keep_first(lo[a], __shfl_xor(lo[a], k));
+            hi[a] = max_keep_first(hi[a], __shfl_xor(hi[a], k));
+        }
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0)
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { red[w][a] = lo[a]; red[w][3 + a] = hi[a]; }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const int a = threadIdx.x;
+        float l = red[0][a], h = red[0][3 + a];
+        for (int k = 1; k < 4; ++k) { l = min_keep_first(l, red[k][a]); h = max_keep_first(h, red[k][3 + a]); }
+        box[a] = l;
+        box[4 + a] = (h > l) ? 1023.0f / (h - l) : 0.0f;
+    }
+}
+
+__global__ __launch_bounds__(256) void morton_code_kernel(uint64_t n, const float* __restrict__ pos4, const float* __restrict__ box,
+                                                          uint32_t* __restrict__ codes) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    uint32_t code = 0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float v = pos4[4 * i + a];
+        uint32_t q = 0u;
+        if (finitef(v)) {
+            float t = (v - box[a]) * box[4 + a];
+            t = (0.0f < t) ? t : 0.0f;                  // std::max(0.0f, t): a NaN product (inf * 0) gives 0
+            t = (t < 1023.0f) ? t : 1023.0f;            // std::min(1023.0f, t)
+            q = (uint32_t)t;
+        }
+        code |= spread3_dev(q) << a;
+    }
+    codes[i] = code;
+}
+
+// table[digit * nwg + workgroup] = keys of the workgroup's tile with that digit
+__global__ __launch_bounds__(256) void radix_hist_kernel(uint64_t n, const uint32_t* __restrict__ keys, uint32_t* __restrict__ table,
+                                                         unsigned int nwg, int shift) {
+    __shared__ unsigned int h[256];
+    h[threadIdx.x] = 0u;
+    __syncthreads();
+    const uint64_t tile0 = (uint64_t)blockIdx.x * SORT_TILE;
+#pragma unroll 4
+    for (int r = 0; r < SORT_ITEMS; ++r) {
+        const uint64_t i = tile0 + (uint64_t)r * 256u + threadIdx.x;
+        if (i < n) atomicAdd(&h[(keys[i] >> shift) & 255u], 1u);          // (a count: the order of arrival does not show)
+    }
+    __syncthreads();
+    table[(uint64_t)threadIdx.x * nwg + blockIdx.x] = h[threadIdx.x];
+}
+
+// One workgroup per digit: its row of the table becomes the exclusive prefix over the workgroups, totals[digit] the row's sum
+// (the scatter adds the digits below its own from `totals`: 256 words)
+__global__ __launch_bounds__(256) void radix_scan_kernel(uint32_t* __restrict__ table, uint32_t* __restrict__ totals, unsigned int nwg) {
+    __shared__ unsigned int wsum[4];
+    uint32_t* row = table + (uint64_t)blockIdx.x * nwg;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    unsigned int carry = 0u;
+    for (unsigned int c0 = 0; c0 < nwg; c0 += 256u) {
+        const unsigned int i = c0 + threadIdx.x;            // (c0 + 255 < 2^32: nwg <= 2^32 / SORT_TILE)
+        const unsigned int v = i < nwg ? row[i] : 0u;
+        const unsigned int incl = wave_inclusive_sum(v);
+        if (lane == 63) wsum[w] = incl;
+        __syncthreads();
+        unsigned int off = carry, all = 0u;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { if (k < w) off += wsum[k]; all += wsum[k]; }
+        if (i < nwg) row[i] = off + incl - v;
+        carry += all;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) totals[blockIdx.x] = carry;
+}
+
+// The stable scatter of one pass.  A tile is taken 256 keys at a time, in index order; within such a round a key's place
+// among the keys of its digit is (keys of the digit in earlier rounds) + (in the waves below its own) + (in the lanes below
+// its own): the first a running LDS counter, the second an LDS table the waves' leaders fill, the third a ballot.
+// vals_in == nullptr: the values are the indices themselves (first pass); keys_out == nullptr: the keys are not needed
+// again (last pass).
+__global__ __launch_bounds__(256) void radix_scatter_kernel(uint64_t n, const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__ vals_in,
+                                                            uint32_t* __restrict__ keys_out, uint32_t* __restrict__ vals_out,
+                                                            const uint32_t* __restrict__ table, const uint32_t* __restrict__ totals,
+                                                            unsigned int nwg, int shift) {
+    __shared__ unsigned int base[256];           // where the tile's next key of each digit goes
+    __shared__ unsigned int wcount[4][256];      // this round: keys of each digit in each wave
+    __shared__ unsigned int wtot[4];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    {   // base[d] = (keys of the digits below d, whole array) + (keys of digit d in the tiles before this one)
+        const unsigned int t = totals[tid];
+        const unsigned int incl = wave_inclusive_sum(t);
+        if (lane == 63) wtot[w] = incl;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) wcount[k][tid] = 0u;
+        __syncthreads();
+        unsigned int off = 0u;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) if (k < w) off += wtot[k];
+        base[tid] = off + incl - t + table[(uint64_t)tid * nwg + blockIdx.x];
+    }
+    __syncthreads();
+    const uint64_t tile0 = (uint64_t)blockIdx.x * SORT_TILE;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (int r = 0; r < SORT_ITEMS; ++r) {
+        const uint64_t i = tile0 + (uint64_t)r * 256u + tid;
+        if (tile0 + (uint64_t)r * 256u >= n) break;          // (uniform: the tile ends here)
+        const bool valid = i < n;
+        const uint32_t key = valid ? keys_in[i] : 0u;
+        const uint32_t val = valid ? (vals_in ? vals_in[i] : (uint32_t)i) : 0u;
+        const unsigned int d = (key >> shift) & 255u;
+        unsigned long long same = __ballot(valid);
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            const bool bit = (d >> b) & 1u;
+            const unsigned long long bal = __ballot(bit);
+            same &= bit ? bal : ~bal;
+        }
+        const unsigned int rank = __popcll(same & below);
+        if (valid && rank == 0u) wcount[w][d] = __popcll(same);
+        __syncthreads();
+        unsigned int off = base[d] + rank;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) if (k < w) off += wcount[k][d];
+        __syncthreads();
+        if (valid) {
+            if (keys_out) keys_out[off] = key;
+            vals_out[off] = val;
+        }
+        {   // thread `tid` keeps digit `tid`'s counter
+            unsigned int all = 0u;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { all += wcount[k][tid]; wcount[k][tid] = 0u; }
+            base[tid] += all;
+        }
+        __syncthreads();
+    }
+}
+
+// Bounds of K1 block blockIdx.x (block_bounds of splat_api.hip): thread t holds slot 256 b + t.  The reductions keep the
+// host loop's order, so the earlier of two equal coordinates is the one that stays.
+__global__ __launch_bounds__(256) void block_bounds_kernel(uint64_t n, const float* __restrict__ pos4, const float* __restrict__ cov3d,
+                                                           const unsigned int* __restrict__ orig, BlockBounds* __restrict__ out) {
+    __shared__ float red[4][7];
+    const uint64_t j = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY}, fmax = 0.0f;
+    if (j < n) {
+        const uint64_t i = orig[j];
+        const float p0 = pos4[4 * i], p1 = pos4[4 * i + 1], p2 = pos4[4 * i + 2];
+        if (finitef(p0) && finitef(p1) && finitef(p2)) {
+            lo[0] = hi[0] = p0; lo[1] = hi[1] = p1; lo[2] = hi[2] = p2;
+            double f2 = 0.0;
+#pragma unroll
+            for (int e = 0; e < 9; ++e) { const double v = (double)cov3d[9 * i + e]; f2 += v * v; }
+            float f = (float)sqrt(f2) * 1.0001f;
+            if (!(f >= 0.0f)) f = INFINITY;                    // NaN: unbounded extent
+            fmax = f;
+        }
+    }
+    // lane l ends up with the lanes l .. 63 in order (strides 1, 2, 4, ...: neighbouring runs joined, the earlier one on the left)
+#pragma unroll
+    for (int k = 1; k < 64; k <<= 1) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = min_keep_first(lo[a], __shfl_down(lo[a], k));
+            hi[a] = max_keep_first(hi[a], __shfl_down(hi[a], k));
+        }
+        fmax = max_keep_first(fmax, __shfl_down(fmax, k));
+    }
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) { red[w][a] = lo[a]; red[w][3 + a] = hi[a]; }
+        red[w][6] = fmax;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        BlockBounds bb;
+        for (int a = 0; a < 3; ++a) {
+            float l = red[0][a], h = red[0][3 + a];
+            for (int k = 1; k < 4; ++k) { l = min_keep_first(l, red[k][a]); h = max_keep_first(h, red[k][3 + a]); }
+            bb.lo[a] = l; bb.hi[a] = h;
+        }
+        float f = red[0][6];
+        for (int k = 1; k < 4; ++k) f = max_keep_first(f, red[k][6]);
+        bb.fmax = f; bb.pad = 0.0f;
+        if (!(bb.lo[0] <= bb.hi[0]))                            // no finite centre at all: NaN bounds answer "maybe"
+            for (int a = 0; a < 3; ++a) { bb.lo[a] = NAN; bb.hi[a] = NAN; }
+        out[blockIdx.x] = bb;
+    }
+}
+
 // Exactly covered pixel interval {p in [lo_lim,hi_lim] : |p + off - c| <= h}; false when empty.
 __device__ __forceinline__ bool covered_interval(float c, float h, float off, int lo_lim, int hi_lim, int* lo, int* hi) {
     float flo = c - h - off, fhi = c + h - off;
@@ -3267,6 +3532,41 @@ void launch_pack_scene(hipStream_t s, uint64_t n, const float* pos4, const float
 void launch_cov3d(hipStream_t s, uint64_t n, const float* scales3, const float* rot4, float* cov3d) {
     if (!n) return;
     hipLaunchKernelGGL(cov3d_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, n, scales3, rot4, cov3d);
+}
+// Scene order on the device.  The small buffer: the (digit, workgroup) table, the 256 digit totals, the partial boxes, the box.
+static inline unsigned int sort_groups(uint64_t n) { return (unsigned int)((n + SORT_TILE - 1) / SORT_TILE); }
+static inline unsigned int box_groups(uint64_t n) { return std::min(blocks_for(n, 256), BOX_GROUPS_MAX); }
+size_t scene_order_small_bytes(uint64_t n) {
+    return sizeof(uint32_t) * (256ull * sort_groups(n) + 256ull) + sizeof(float) * (8ull * box_groups(n) + 8ull);
+}
+void launch_scene_order(hipStream_t s, uint64_t n, const float* pos4, uint32_t* pingpong, void* small, unsigned int* orig,
+                        hipEvent_t sort_begin, hipEvent_t sort_end) {
+    if (!n) return;
+    const unsigned int nwg = sort_groups(n), ngr = box_groups(n);
+    uint32_t *k0 = pingpong, *k1 = pingpong + n, *v0 = pingpong + 2 * n, *v1 = pingpong + 3 * n;
+    uint32_t* table = (uint32_t*)small;
+    uint32_t* totals = table + 256ull * nwg;
+    float* partial = (float*)(totals + 256);
+    float* box = partial + 8ull * ngr;
+    hipLaunchKernelGGL(scene_box_kernel, dim3(ngr), dim3(256), 0, s, n, pos4, partial);
+    hipLaunchKernelGGL(scene_box_final_kernel, dim3(1), dim3(256), 0, s, ngr, partial, box);
+    hipLaunchKernelGGL(morton_code_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, n, pos4, box, k0);
+    if (sort_begin) (void)hipEventRecord(sort_begin, s);
+    // four 8-bit passes over the 30-bit codes: k0 -> (k1, v1) -> (k0, v0) -> (k1, v1) -> orig
+    const uint32_t* kin = k0; const uint32_t* vin = nullptr;
+    for (int pass = 0; pass < 4; ++pass) {
+        uint32_t* kout = pass == 3 ? nullptr : ((pass & 1) ? k0 : k1);
+        uint32_t* vout = pass == 3 ? (uint32_t*)orig : ((pass & 1) ? v0 : v1);
+        hipLaunchKernelGGL(radix_hist_kernel, dim3(nwg), dim3(256), 0, s, n, kin, table, nwg, 8 * pass);
+        hipLaunchKernelGGL(radix_scan_kernel, dim3(256), dim3(256), 0, s, table, totals, nwg);
+        hipLaunchKernelGGL(radix_scatter_kernel, dim3(nwg), dim3(256), 0, s, n, kin, vin, kout, vout, table, totals, nwg, 8 * pass);
+        kin = kout; vin = vout;
+    }
+    if (sort_end) (void)hipEventRecord(sort_end, s);
+}
+void launch_block_bounds(hipStream_t s, uint64_t n, const float* pos4, const float* cov3d, const unsigned int* orig, BlockBounds* bounds) {
+    if (!n) return;
+    hipLaunchKernelGGL(block_bounds_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, n, pos4, cov3d, orig, bounds);
 }
 void launch_preprocess(hipStream_t s, uint64_t n, const float4* planes, const unsigned int* orig, FrameConst fc, Rec* recs,
                        float* depth, ushort4* rect, unsigned int* counts, unsigned int* vislist, unsigned long long* keys,

@@ -32,9 +32,66 @@ class GaussianList:
         self.cov3d = renderer.compute_cov3d(self.scales, self.rotations)
         return self
 
+    def to_device(self, renderer):
+        """The six buffers in the renderer's GPU memory (splat_device_alloc + splat_device_upload): what a caller without
+        torch hands to Renderer.upload_device / compute_cov3d_device.  free() them when done."""
+        return DeviceGaussians(renderer, self)
+
     def subset(self, idx):
         return GaussianList(self.positions[idx], self.scales[idx], self.opacities[idx], self.rotations[idx],
                             self.sh[idx], self.cov3d[idx])
+
+
+class DeviceGaussians:
+    """Device addresses (ints) of a GaussianList's buffers on one renderer's GPU: positions, scales, opacities, rotations,
+    sh, cov3d; n Gaussians.  Allocations of that renderer's context (they count in its device_bytes()), owned by this object:
+    free() them before the renderer is closed.  Any context on the same GPU may read them."""
+    FIELDS = ("positions", "scales", "opacities", "rotations", "sh", "cov3d")
+
+    def __init__(self, renderer, g):
+        import ctypes as C
+        self._r = renderer
+        self.n = len(g)
+        for k in self.FIELDS:
+            setattr(self, k, 0)
+        for k in self.FIELDS:
+            a = getattr(g, k)
+            if a.nbytes:
+                setattr(self, k, self._alloc(a.nbytes))
+                renderer._check(renderer._L.splat_device_upload(renderer._h, C.c_void_p(getattr(self, k)),
+                                                                C.c_void_p(a.ctypes.data), a.nbytes))
+
+    def _alloc(self, nbytes):
+        p = self._r._L.splat_device_alloc(self._r._h, nbytes)
+        if not p:
+            self.free()
+            raise MemoryError("splat_device_alloc(%d)" % nbytes)
+        return p
+
+    def update(self, field, array):
+        """overwrite one buffer from a host array of the same size (an edit of the scene in place)"""
+        import ctypes as C
+        a = np.ascontiguousarray(array, f32)
+        if field not in self.FIELDS or not getattr(self, field):
+            raise ValueError("no device buffer %r" % field)
+        self._r._check(self._r._L.splat_device_upload(self._r._h, C.c_void_p(getattr(self, field)), C.c_void_p(a.ctypes.data), a.nbytes))
+
+    def compute_cov3d(self):
+        """cov3d from scales and rotations, device to device (kernel K0)"""
+        if self.n:
+            self._r.compute_cov3d_device(self.scales, self.rotations, self.cov3d, n=self.n)
+        return self
+
+    def upload(self):
+        """make this the renderer's scene (Renderer.upload_device)"""
+        self._r.upload_device(self.positions, self.cov3d, self.opacities, self.sh, n=self.n)
+        return self
+
+    def free(self):
+        for k in self.FIELDS:
+            if getattr(self, k, 0) and getattr(self._r, "_h", None):
+                self._r.device_free(getattr(self, k))
+            setattr(self, k, 0)
 
 
 def naive_gaussians():

@@ -1,5 +1,6 @@
 """Thin object wrapper over the C ABI context (include/splat_hip.h)."""
 import ctypes as C
+import sys
 
 import numpy as np
 
@@ -17,6 +18,62 @@ class SplatError(RuntimeError):
 def _fp(a):
     assert a.dtype == np.float32 and a.flags.c_contiguous
     return a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def _device_address(a, what, floats, device):
+    """Device address of one scene buffer: an int is taken as it is; anything with data_ptr() (a torch tensor -- the
+    package itself never imports torch) is checked as far as it describes itself: float32, contiguous, on the context's
+    GPU, `floats` elements (None: not known yet)."""
+    if isinstance(a, int):
+        if a < 0:
+            raise ValueError("%s: a device address is not negative" % what)
+        return a
+    if not hasattr(a, "data_ptr"):
+        raise TypeError("%s: expected a device address (int) or an object with data_ptr(), got %s" % (what, type(a).__name__))
+    dt = getattr(a, "dtype", None)
+    if dt is not None and str(dt).rsplit(".", 1)[-1] != "float32":
+        raise TypeError("%s: float32 expected, got %s" % (what, dt))
+    if hasattr(a, "is_contiguous") and not a.is_contiguous():
+        raise ValueError("%s: not contiguous" % what)
+    dev = getattr(a, "device", None)
+    if dev is not None and hasattr(dev, "type"):
+        if dev.type != "cuda":
+            raise ValueError("%s: lives on %s, not on a GPU" % (what, dev))
+        if dev.index is not None and dev.index != device:
+            raise ValueError("%s: lives on GPU %d, the context on GPU %d" % (what, dev.index, device))
+    if floats is not None and hasattr(a, "numel") and int(a.numel()) != floats:
+        raise ValueError("%s: %d floats expected, got %d" % (what, floats, int(a.numel())))
+    return int(a.data_ptr())
+
+
+def _count_of(a, per, n):
+    """Gaussians in buffer `a` of `per` floats each: from its numel() unless the caller said n=."""
+    if n is not None:
+        return int(n)
+    if isinstance(a, int) or not hasattr(a, "numel"):
+        raise TypeError("n= is required with plain device addresses")
+    m = int(a.numel())
+    if m % per:
+        raise ValueError("%d floats are not a whole number of Gaussians (%d floats each)" % (m, per))
+    return m // per
+
+
+def _producer_stream(stream, args):
+    """The hipStream_t the caller's writes were enqueued on.  None: torch's current stream when the buffers are torch's
+    (looked up only if the caller has imported torch -- this package does not), else 0 = the caller has synchronised."""
+    if stream is not None:
+        return int(getattr(stream, "cuda_stream", stream))
+    torch = sys.modules.get("torch")
+    if torch is not None:
+        t = next((a for a in args if isinstance(a, torch.Tensor)), None)
+        if t is not None:
+            cur = torch.cuda.current_stream(t.device)
+            if not int(cur.cuda_stream):
+                # the legacy default stream has no handle to record an event on (NULL means "already synchronised" to
+                # the library), and the context's streams do not wait for it by themselves
+                cur.synchronize()
+            return int(cur.cuda_stream)
+    return 0
 
 
 class Renderer:
@@ -73,6 +130,45 @@ class Renderer:
         out = np.zeros((n, 9), f32)
         self._check(self._L.splat_compute_cov3d(self._h, n, _fp(scales), _fp(rotations), _fp(out)))
         return out
+
+    def upload_device(self, positions, cov3d, opacities, sh, stream=None, n=None):
+        """splat_upload_scene_device: the scene from buffers that are already in this GPU's memory (layouts of upload():
+        positions [n,4], cov3d [n,9], opacities [n], sh [n,48], float32).  Each one is a device address (int, with n=) or
+        an object with data_ptr().  stream: the hipStream_t (or torch stream) the buffers were written on; the library
+        waits for that work, not the caller.  Synchronous: the buffers are free again on return.  The frames that follow
+        are those of upload() of the same data, byte for byte."""
+        if hasattr(positions, "positions") and n is None:      # a DeviceGaussians (GaussianList.to_device)
+            n = positions.n
+        if hasattr(positions, "positions"):
+            positions = positions.positions
+        n = _count_of(positions, 4, n)
+        dev = int(self.config.device)
+        ptrs = [_device_address(a, what, per * n, dev) for a, what, per in
+                ((positions, "positions", 4), (cov3d, "cov3d", 9), (opacities, "opacities", 1), (sh, "sh", 48))]
+        st = _producer_stream(stream, (positions, cov3d, opacities, sh))
+        self._check(self._L.splat_upload_scene_device(self._h, n, *[C.c_void_p(p) for p in ptrs], C.c_void_p(st)))
+        self.n = n
+
+    def compute_cov3d_device(self, scales, rotations, out, stream=None, n=None):
+        """splat_compute_cov3d_device: kernel K0 from device buffers (scales [n,3], rotations [n,4]) into a device buffer
+        (out [n,9]); arguments and stream as in upload_device.  Returns when `out` is written."""
+        n = _count_of(scales, 3, n)
+        dev = int(self.config.device)
+        ptrs = [_device_address(a, what, per * n, dev) for a, what, per in
+                ((scales, "scales", 3), (rotations, "rotations", 4), (out, "out", 9))]
+        st = _producer_stream(stream, (scales, rotations, out))
+        self._check(self._L.splat_compute_cov3d_device(self._h, n, *[C.c_void_p(p) for p in ptrs], C.c_void_p(st)))
+        return out
+
+    def scene_layout(self):
+        """(orig, bounds) of the current scene: orig[j] = the Gaussian stored in slot j (uint32 [n]); bounds = per K1 block
+        of 256 slots lo[3], hi[3], fmax, pad (float32 [ceil(n/256), 8])."""
+        nb = (self.n + 255) // 256
+        orig = np.zeros(self.n, np.uint32)
+        bounds = np.zeros((nb, 8), f32)
+        self._check(self._L.splat_get_scene_layout(self._h, orig.ctypes.data_as(C.POINTER(C.c_uint32)), self.n,
+                                                   bounds.ctypes.data_as(C.POINTER(C.c_float)), nb))
+        return orig, bounds
 
     def set_slab(self, tile_row0=0, tile_row1=-1):
         self._check(self._L.splat_set_slab(self._h, int(tile_row0), int(tile_row1)))
