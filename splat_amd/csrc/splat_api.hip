@@ -33,7 +33,6 @@ constexpr int N_TIMES = 6;     // preprocess, scan, emit, sort, composite, statu
 constexpr int EV_RING = 32;
 static_assert(EV_RING == SPLAT_POLICY_RING, "the frame policy sees the whole status ring");
 constexpr int N_SLOTS = 4;
-constexpr unsigned int HINT_WORDS = 13u;   // per tile (need_hint): 4 walks' needs, the selection's depth, 4 walks' starts, 4 starts' refinement states
 
 struct EvSet {
     hipEvent_t e[N_EV];
@@ -101,8 +100,6 @@ struct splat_ctx {
     uint64_t cap2 = 0;                     // entries in each used slot's second key buffer (0: none).  Two-pass binning: a mirror of the first
                                            // (cap2 == cap); one-pass: room for the lists of more than 2048 keys only (default_keys2_capacity)
     uint64_t keys2_want = 0;               // a harvested frame's long lists outgrew the second key buffer: grow to this
-    // one-pass binning (per-tile buckets): on unless SPLAT_BUCKETS=0, the caller fixed pair_capacity,
-    // the buckets would not fit bucket_bytes, or a tile outgrew the largest LDS-sortable bucket
     // one-pass binning (per-tile regions of the key buffer, sized from earlier frames' lists): on unless SPLAT_BUCKETS=0, the
     // caller fixed pair_capacity, or the key buffers would not fit bucket_bytes
     bool use_buckets = true;
@@ -214,8 +211,8 @@ struct splat_ctx {
                                            // a camera at rest; 2 nor, three frames of four, with one in slow motion (see enqueue_frame)
     bool one_pass_select = true;           // SPLAT_DBG_ONE_PASS_SELECT=0: near selection always takes its two passes (histogram, compaction)
     int start_refine = 1;                  // SPLAT_OPT_START_REFINE / SPLAT_START_REFINE: a camera at rest refines its walks' starts (splat_policy_decision::refine)
-    unsigned int* need_hint = nullptr;     // 4 x m_alloc words: per tile and wave, the nearest keys its walk needed in the most recent frame
-                                           // (HINT_WORDS x m_alloc in all: the selections' depths, the walks' starts and their refinement behind them)
+    unsigned int* need_hint = nullptr;     // the per-tile hint table (HintTable of splat_internal.h, m_alloc words a plane: hint_table() below): first in
+                                           // it, per tile and wave, the nearest keys its walk needed in the most recent frame
     bool last_near = false;                // the most recent frame ran with near selection: its long lists are unordered in memory
     int timing_every = 8;                  // SPLAT_TIMING_EVERY: per-kernel events on every n-th frame (and whenever stats are asked for)
     int pipeline = 6;                      // frames in flight on the device (SPLAT_PIPELINE = 1..6, see enqueue_frame)
@@ -522,6 +519,11 @@ int ensure_lane(splat_ctx* c) {
     return SPLAT_OK;
 }
 
+// the context's scene and hint table as the launches' argument blocks name them (a table about to be made: its stride given)
+SceneArgs scene_of(const splat_ctx* c) { return {c->n, c->planes, c->orig, c->bounds}; }
+HintTable hint_table(const splat_ctx* c, size_t stride) { return {c->need_hint, stride}; }
+HintTable hint_table(const splat_ctx* c) { return hint_table(c, c->m_alloc); }
+
 int ensure_bins(splat_ctx* c, unsigned int m) {
     if (m + 1 <= c->m_alloc) return SPLAT_OK;
     int rc = sync_all(c);
@@ -532,8 +534,8 @@ int ensure_bins(splat_ctx* c, unsigned int m) {
     HIP_TRY(c, dmalloc(c, &c->zero_layout, sizeof(unsigned int) * (size_t)(m + 1)));
     HIP_TRY(c, fill_now(c->zero_layout, 0, sizeof(unsigned int) * (size_t)(m + 1)));
     dfree(c->need_hint);
-    HIP_TRY(c, dmalloc(c, &c->need_hint, sizeof(unsigned int) * HINT_WORDS * (size_t)(m + 1)));      // (+ one word per tile behind them: the depth its last selection began at; + four: where its waves' walks started; + four: their refinement)
-    HIP_TRY(c, fill_now(c->need_hint, 0, sizeof(unsigned int) * HINT_WORDS * (size_t)(m + 1)));
+    HIP_TRY(c, dmalloc(c, &c->need_hint, hint_table(c, (size_t)(m + 1)).bytes()));
+    HIP_TRY(c, fill_now(c->need_hint, 0, hint_table(c, (size_t)(m + 1)).bytes()));
     for (Slot& s : c->slots) {
         dfree(s.counts); dfree(s.offsets); dfree(s.cursor); dfree(s.order); dfree(s.lens); dfree(s.counts_b); dfree(s.lay_a); dfree(s.lay_b);
         dfree(s.near_m); dfree(s.redo_layout); dfree(s.redo_cursors); dfree(s.off2);
@@ -620,7 +622,6 @@ uint64_t default_pair_capacity(const splat_ctx* c) {
 // tile) left none.  C3s at 3 / 10 degrees a frame: 1450 / 1340 frames/s with 16 N, 1650 / 1340 with 32 N, 1725 / 1460 with 64 N
 // (frames no longer binned twice); 36 uncorrelated synchronous poses 602 -> 811 -> 825 frames/s.  2.3 -> 6.1 GB of device
 // memory on C3, 14.8 -> 15.4 GB on C5 (32 N), of 288.
-int slots_in_use(const splat_ctx* c);
 uint64_t region_capacity_for(const splat_ctx* c, uint64_t mult) { return std::max<uint64_t>(1ull << 22, mult * c->n); }
 // The second key buffer of a one-pass frame slot: room for the lists of more than 2048 keys (the scan hands it out).  12
 // entries per Gaussian hold every frame measured (C3's bench pose asks for 5.3 M of 18 M, the surface scene from inside
@@ -694,72 +695,57 @@ int build_frame_const(splat_ctx* c, const splat_camera* cam, FrameConst* fc, uns
     return SPLAT_OK;
 }
 
-// Enqueue one frame.  Never blocks the host unless the event ring wraps onto a frame that is
-// still running (32 frames behind).
-// `timed`: record the per-kernel timing events.  Every hipEventRecord is a barrier packet that
-// drains its queue for a few microseconds -- nine of them per frame were ~25 us of bubbles in a
-// 590 us frame -- so untimed frames (all but every `timing_every`-th of an asynchronous run) record
-// only the one event that tells the host the frame's status has arrived.
-int enqueue_frame(splat_ctx* c, uint32_t* d_argb, bool timed, bool want_iters = false, bool may_overlap = false, bool awaited = false) {
-    use_launch_knobs(&c->knobs);
-    const int r = c->ring_next;
-    EvSet& ev = c->ring[r];
-    auto mark = [&](int k, hipStream_t st) -> hipError_t { return timed ? hipEventRecord(ev.e[k], st) : hipSuccess; };
-    c->ring_next = (c->ring_next + 1) % EV_RING;
-    harvest(c, r);
-    std::memset(&c->h_status[r], 0, sizeof(FrameStatus));      // (this frame's scan fills it; until then it says nothing: see the peek below)
-    const int si = (int)(c->frame_idx++ % (uint64_t)slots_in_use(c));
-    Slot& s = c->slots[si];
-    FrameStatus* const d_st = c->d_status_ring + r;       // (initialised by this frame's scan)
-    // pipeline depth 1: everything on the caller's stream.  2: K1..K3 of frame N+1 on the bin stream
-    // under the compositor of frame N.  3: K1 + scan of frame N+2 on the bin stream, K2 + K3 of
-    // frame N+1 on the sort stream, compositor of frame N on the caller's stream -- the bin chain is
-    // the longest of the three under contention, so splitting it raises the frame rate.
-    hipStream_t bs = c->pipeline ? c->bin_stream : c->stream;
-    // 6 (default): four slots, and the bin + sort chains of consecutive frames alternate between two streams, so
-    // the chain of frame N+2 (a latency chain: K1 -> scan -> sort) runs beside the chain of frame N+1 and the
-    // compositor of frame N.  With one chain at a time the frame time IS the chain's length under contention
-    // (C3: 0.28 + 0.03 + 0.11 = 0.42 ms against a compositor of 0.37); two in flight leave the compositor as the
-    // bound: C3 2241 -> 2334 fps, C1 17.4 k -> 19.2 k, C5 +1 %, C2 -1 %
-    if (c->pipeline >= 6 && (c->frame_idx & 1ull)) bs = c->sort_stream;
-    hipStream_t ss = c->pipeline == 3 ? c->sort_stream : bs;     // (4, 5: three / four slots on two streams)
-    // A frame the caller waits for, with nothing else in flight (the reference's loop: one synchronous frame per pose,
-    // src/main.rs:69-78), has nothing to overlap with: its whole chain goes on the caller's stream, in order -- no event
-    // recorded on one stream and waited for on another between its binning and its compositor (two barrier packets and a
-    // cross-queue hand-over: ~15 us of a 0.6-ms frame).
-    const unsigned int m = c->n_tiles;
-    // THE FRAME'S DECISIONS (include/splat_policy.h): everything below this call only launches what it says.
+// What the stages of enqueue_frame share: filled once, as the frame's ring entry, slot, decisions and streams become known.
+struct FrameLaunch {
+    int r;                      // the frame's entry of the event / status ring
+    EvSet* ev;
+    bool timed;
+    int si;                     // the frame's slot
+    Slot* s;
+    FrameStatus* d_st;          // (initialised by this frame's scan)
     splat_policy_decision pd;
-    {
-        splat_policy_knobs pk;
-        pk.start_hints = c->start_hints | (c->start_refine ? 0 : SPLAT_POLICY_NO_REFINE); pk.count_first = c->count_first; pk.overflow_redo = c->overflow_redo; pk.early_min = c->early_min;
-        pk.early_eps = c->early_eps; pk.near_cap = c->near_cap; pk.fused_sort_max = c->fused_sort_max; pk.sort_in_comp = c->sort_in_comp;
-        pk.pair_mode = c->pair_mode; pk.pipeline = c->pipeline; pk.tight_grids = c->tight_grids ? 1 : 0;
-        pk.large_list_min = c->large_tiles < 0 ? -1 : c->large_list_min; pk.layout_motion = c->layout_motion;
-        splat_policy_input pi;
-        std::memset(&pi, 0, sizeof pi);
-        std::memcpy(pi.view, c->fc.view, sizeof pi.view); std::memcpy(pi.proj, c->fc.proj, sizeof pi.proj);
-        pi.w = c->fc.w; pi.h = c->fc.h; pi.htanx = c->fc.htanx; pi.htany = c->fc.htany; pi.focal = c->fc.focal;
-        std::memcpy(pi.cam, c->fc.cam, sizeof pi.cam); pi.lowpass = c->fc.lowpass;
-        pi.tile_row0 = c->fc.tile_row0; pi.n_tile_rows = c->fc.n_tile_rows;
-        pi.frame_idx = c->frame_idx; pi.ring_entry = r; pi.one_pass = c->fc.bucket_cap ? 1 : 0;
-        pi.layout_valid = s.layout_valid ? 1 : 0; pi.layout_cam = s.layout_cam[s.flip];
-        pi.awaited = awaited ? 1 : 0; pi.idle = c->idle ? 1 : 0; pi.has_keys2 = s.keys2 != nullptr ? 1 : 0; pi.n_tiles = m;
-        pi.sort_hint = c->sort_hint ? 1 : 0; pi.hint_maxlen = c->hint_maxlen; pi.hint_ge2048 = c->hint_ge2048; pi.hint_ge8192 = c->hint_ge8192;
-        pi.hint_ge16384 = c->hint_ge16384; pi.hint_pairs = c->hint_pairs; pi.hint_large = c->hint_large; pi.hint_window = c->hint_window;
-        for (int q = 0; q < EV_RING; ++q) {      // (the scans of frames in flight write these words to the host: a peek, no wait)
-            const volatile FrameStatus* hs = &c->h_status[q];
-            pi.status[q].in_flight = c->ring[q].used ? 1u : 0u; pi.status[q].arrived = hs->arrived;
-            pi.status[q].overflow = hs->overflow; pi.status[q].redone = hs->redone;
-        }
-        if (splat_policy_decide(&pk, &c->pol, &pi, &pd) != 0) return fail(c, SPLAT_ERR_INVALID, "frame policy refused its input");
-        c->pol = pd.next;
+    hipStream_t bs, ss, cs;     // binning, ordering, compositor
+    TileLists lists;
+    KeyBuffers keys;
+    hipError_t mark(int k, hipStream_t st) const { return timed ? hipEventRecord(ev->e[k], st) : hipSuccess; }
+};
+
+// The frame policy's view of the context: its knobs ...
+splat_policy_knobs policy_knobs_of(const splat_ctx* c) {
+    splat_policy_knobs pk;
+    pk.start_hints = c->start_hints | (c->start_refine ? 0 : SPLAT_POLICY_NO_REFINE); pk.count_first = c->count_first; pk.overflow_redo = c->overflow_redo; pk.early_min = c->early_min;
+    pk.early_eps = c->early_eps; pk.near_cap = c->near_cap; pk.fused_sort_max = c->fused_sort_max; pk.sort_in_comp = c->sort_in_comp;
+    pk.pair_mode = c->pair_mode; pk.pipeline = c->pipeline; pk.tight_grids = c->tight_grids ? 1 : 0;
+    pk.large_list_min = c->large_tiles < 0 ? -1 : c->large_list_min; pk.layout_motion = c->layout_motion;
+    return pk;
+}
+// ... and its input: the camera, the slot's regions, the last harvested frame's list profile, the statuses of the frames in flight
+splat_policy_input policy_input_of(const splat_ctx* c, const Slot& s, int ring_entry, bool awaited) {
+    splat_policy_input pi;
+    std::memset(&pi, 0, sizeof pi);
+    std::memcpy(pi.view, c->fc.view, sizeof pi.view); std::memcpy(pi.proj, c->fc.proj, sizeof pi.proj);
+    pi.w = c->fc.w; pi.h = c->fc.h; pi.htanx = c->fc.htanx; pi.htany = c->fc.htany; pi.focal = c->fc.focal;
+    std::memcpy(pi.cam, c->fc.cam, sizeof pi.cam); pi.lowpass = c->fc.lowpass;
+    pi.tile_row0 = c->fc.tile_row0; pi.n_tile_rows = c->fc.n_tile_rows;
+    pi.frame_idx = c->frame_idx; pi.ring_entry = ring_entry; pi.one_pass = c->fc.bucket_cap ? 1 : 0;
+    pi.layout_valid = s.layout_valid ? 1 : 0; pi.layout_cam = s.layout_cam[s.flip];
+    pi.awaited = awaited ? 1 : 0; pi.idle = c->idle ? 1 : 0; pi.has_keys2 = s.keys2 != nullptr ? 1 : 0; pi.n_tiles = c->n_tiles;
+    pi.sort_hint = c->sort_hint ? 1 : 0; pi.hint_maxlen = c->hint_maxlen; pi.hint_ge2048 = c->hint_ge2048; pi.hint_ge8192 = c->hint_ge8192;
+    pi.hint_ge16384 = c->hint_ge16384; pi.hint_pairs = c->hint_pairs; pi.hint_large = c->hint_large; pi.hint_window = c->hint_window;
+    for (int q = 0; q < EV_RING; ++q) {      // (the scans of frames in flight write these words to the host: a peek, no wait)
+        const volatile FrameStatus* hs = &c->h_status[q];
+        pi.status[q].in_flight = c->ring[q].used ? 1u : 0u; pi.status[q].arrived = hs->arrived;
+        pi.status[q].overflow = hs->overflow; pi.status[q].redone = hs->redone;
     }
-    // A frame the caller waits for, with nothing else in flight, has nothing to overlap with: its whole chain goes on the
-    // caller's stream, in order (pd.solo)
-    const bool solo = pd.solo != 0;
-    if (solo) { bs = c->stream; ss = c->stream; }
-    c->idle = false;
+    return pi;
+}
+
+// THE BINNING STAGE, on f.bs: the count-first bootstrap, K1 + the large list, the scan (with the next slot's layout), the overflow redo.
+int bin_frame(splat_ctx* c, const FrameLaunch& f) {
+    Slot& s = *f.s;
+    const splat_policy_decision& pd = f.pd;
+    hipStream_t bs = f.bs;
+    const unsigned int m = c->n_tiles;
     if (c->pipeline) {
         // order this frame's binning after whatever the caller queued before the call (it may have
         // written the scene-independent inputs we read? no -- but it keeps stream semantics intact
@@ -772,59 +758,60 @@ int enqueue_frame(splat_ctx* c, uint32_t* d_argb, bool timed, bool want_iters = 
     if (!c->fc.bucket_cap) {                               // two-pass binning: K1 counts visible Gaussians into the status before the scan
         int rc2 = ensure_two_pass_buffers(c, s);
         if (rc2 != SPLAT_OK) return rc2;
-        HIP_TRY(c, hipMemsetAsync(d_st, 0, sizeof(FrameStatus), bs));
+        HIP_TRY(c, hipMemsetAsync(f.d_st, 0, sizeof(FrameStatus), bs));
     }
+    const uint64_t cam_hash = pd.cam_hash;      // (what places the Gaussians on the target: the camera and the slab)
+    c->fc.start_hints = pd.start_hints_mode; c->fc.start_light = pd.start_light; c->fc.early_min = pd.early_min;
+    BinArgs k1{};
+    k1.s = bs; k1.knobs = &c->knobs; k1.scene = scene_of(c); k1.fc = c->fc;
+    k1.recs = s.recs; k1.depth = s.depth; k1.rect = s.rect; k1.vislist = s.vislist; k1.keys = s.keys; k1.blockinfo = s.blockinfo; k1.status = f.d_st;
+    // (no list: K1's blocks expand their close-ups themselves, and only count the large splats)
+    k1.large = {pd.use_large_list ? s.large_list : nullptr, s.large_count, (unsigned int)c->n};
     // One-pass binning: the tiles' regions of the key buffer and their cursors.  Normally the layout_kernel of the frame
     // before this one ON THIS STREAM has left them in the slot's other copy (below); a slot without a layout (first
     // frames, a new scene / target / slab, after a frame outgrew a region) counts its pairs first -- K1 against the
     // empty layout drops every key and counts every pair -- and builds regions that fit exactly this camera.
-    unsigned int *cursors = s.counts, *layout = nullptr;
-    const uint64_t cam_hash = pd.cam_hash;      // (what places the Gaussians on the target: the camera and the slab)
-    uint4* const large_list = pd.use_large_list ? s.large_list : nullptr;       // (no list: K1's blocks expand their close-ups themselves, and only count the large splats)
-    c->fc.start_hints = pd.start_hints_mode; c->fc.start_light = pd.start_light; c->fc.early_min = pd.early_min;
+    k1.bin = {s.counts, nullptr};
     if (c->fc.bucket_cap) {
         // COUNT FIRST (pd.count_first): the frame counts its pairs per tile (K1's count flavour: geometry planes only, no SH, no
         // record, no key -- a third of a K1) and bins into regions that fit exactly ITS camera.
-        const bool count_first = pd.count_first != 0;
-        if (count_first) {
+        if (pd.count_first != 0) {
             const int into = s.layout_valid ? s.flip : 1;
             HIP_TRY(c, hipMemsetAsync(s.redo_cursors, 0, sizeof(unsigned int) * ((size_t)m + 1), bs));     // (the redo's buffer: a count-first frame has no redo)
-            launch_preprocess(bs, c->n, c->planes, c->orig, c->fc, s.recs, s.depth, s.rect, s.redo_cursors, s.vislist, s.keys, c->bounds, s.blockinfo, d_st, c->zero_layout, true,
-                              large_list, s.large_count);
-            launch_bin_large(bs, c->fc, large_list, s.large_count, (unsigned int)c->n, s.redo_cursors, s.keys, d_st, true);
-            launch_layout(bs, m, s.redo_cursors, c->zero_layout, into ? s.lay_b : s.lay_a, into ? s.counts_b : s.counts, c->fc.bucket_cap, nullptr, nullptr, c->region_spare,
-                          nullptr, s.large_count);
+            BinArgs count = k1;
+            count.bin = {s.redo_cursors, c->zero_layout}; count.count_only = true;
+            launch_preprocess(count); launch_bin_large(count);
+            LayoutArgs lay{};
+            lay.s = bs; lay.m = m; lay.from = count.bin; lay.next = {into ? s.counts_b : s.counts, into ? s.lay_b : s.lay_a};
+            lay.key_entries = c->fc.bucket_cap; lay.spare_max = c->region_spare; lay.large_count = s.large_count;
+            launch_layout(lay);
             s.flip = into; s.layout_valid = true;
             s.layout_cam[into] = cam_hash;
         }
-        cursors = s.flip ? s.counts_b : s.counts;
-        layout = s.flip ? s.lay_b : s.lay_a;
+        k1.bin = {s.flip ? s.counts_b : s.counts, s.flip ? s.lay_b : s.lay_a};
     }
-    HIP_TRY(c, mark(0, bs));
-    launch_preprocess(bs, c->n, c->planes, c->orig, c->fc, s.recs, s.depth, s.rect, cursors, s.vislist, s.keys, c->bounds, s.blockinfo, d_st, layout, false,
-                      large_list, s.large_count);
-    if (c->fc.bucket_cap) launch_bin_large(bs, c->fc, large_list, s.large_count, (unsigned int)c->n, cursors, s.keys, d_st, false);     // (the large splats K1 listed, tile by tile)
-    HIP_TRY(c, mark(1, bs));
+    HIP_TRY(c, f.mark(0, bs));
+    launch_preprocess(k1);
+    if (c->fc.bucket_cap) launch_bin_large(k1);     // (the large splats K1 listed, tile by tile)
+    HIP_TRY(c, f.mark(1, bs));
     c->grid_big = pd.grid_big; c->grid_mid = pd.grid_mid; c->grid_long = pd.grid_long;      // (what the sort launches cover; the scan validates)
+    ScanArgs scan{};
+    scan.s = bs; scan.knobs = &c->knobs; scan.m = m; scan.bin = k1.bin; scan.lists = f.lists; scan.keys = f.keys; scan.bucket_cap = c->fc.bucket_cap;
+    scan.grids = {c->grid_big, c->grid_mid, c->grid_long}; scan.status = f.d_st; scan.host_status = &c->h_status[f.r];
+    scan.spare_max = c->region_spare; scan.large_count = s.large_count;
     // (one-pass binning: a second workgroup of the scan's launch builds the regions of the NEXT frame on this binning
     // stream -- two frames on with two chains in flight -- from this frame's lists, into that slot's idle copy)
-    unsigned int *next_layout = nullptr, *next_counts = nullptr;
     if (c->fc.bucket_cap) {
         const int stride = (c->pipeline >= 6) ? 2 : 1;
-        Slot& nx = c->slots[(si + stride) % slots_in_use(c)];
+        Slot& nx = c->slots[(f.si + stride) % slots_in_use(c)];
         const int into = (&nx == &s) ? (s.flip ^ 1) : (nx.layout_valid ? (nx.flip ^ 1) : 1);
-        next_layout = into ? nx.lay_b : nx.lay_a; next_counts = into ? nx.counts_b : nx.counts;
+        scan.next.to = {into ? nx.counts_b : nx.counts, into ? nx.lay_b : nx.lay_a};
         nx.flip = into; nx.layout_valid = true;
         nx.layout_cam[into] = cam_hash;
     }
-    const bool comp_sorts_frame = pd.comp_sorts != 0;
-    const unsigned int near_cap = pd.near_cap;
-    unsigned int* const off2 = c->fc.bucket_cap ? s.off2 : nullptr;        // (two-pass binning: the second buffer mirrors the first)
-    launch_scan(bs, m, cursors, s.offsets, s.cursor, s.order, s.lens, d_st, c->cap, c->fc.bucket_cap, c->grid_big, c->grid_mid, c->grid_long, &c->h_status[r], layout,
-                next_layout, next_counts, c->region_spare, false, off2, (unsigned int)std::min<uint64_t>(c->cap2, 0xffffffffull), s.large_count,
-                (unsigned int)c->fc.tiles_x, (unsigned int)pd.layout_radius);
-    const bool redo = pd.redo != 0;
-    if (redo) {
+    scan.next.tiles_x = (unsigned int)c->fc.tiles_x; scan.next.motion_radius = (unsigned int)pd.layout_radius;
+    launch_scan(scan);
+    if (pd.redo != 0) {
         // OVERFLOW REDO.  The regions this frame was binned into were sized for another camera (two frames back on a moving
         // path): if the scan above found a list beyond its region, the frame is binned again right here -- regions that
         // fit exactly this camera (from the counts the first pass left), K1, scan -- into copies of their own; if not
@@ -833,79 +820,113 @@ int enqueue_frame(splat_ctx* c, uint32_t* d_argb, bool timed, bool want_iters = 
         // (No count pass: K1's reservations keep counting past a region's end -- cursor minus region start IS the tile's exact
         // pair count, overflowed or not (the scan's `raw`) -- and the scan leaves cursors and regions alone: the regions that
         // fit this camera are built straight from them.  One K1 where round 5 ran two.)
-        FrameConst fr = c->fc;
-        fr.redo_only = 1;
-        launch_layout(bs, m, cursors, layout, s.redo_layout, s.redo_cursors, c->fc.bucket_cap, nullptr, nullptr, c->region_spare, d_st);
-        launch_preprocess(bs, c->n, c->planes, c->orig, fr, s.recs, s.depth, s.rect, s.redo_cursors, s.vislist, s.keys, c->bounds, s.blockinfo, d_st, s.redo_layout, false,
-                          large_list, s.large_count);
-        launch_bin_large(bs, fr, large_list, s.large_count, (unsigned int)c->n, s.redo_cursors, s.keys, d_st, false);
-        launch_scan(bs, m, s.redo_cursors, s.offsets, s.cursor, s.order, s.lens, d_st, c->cap, c->fc.bucket_cap, c->grid_big, c->grid_mid, c->grid_long, &c->h_status[r], s.redo_layout,
-                    nullptr, nullptr, c->region_spare, true, off2, (unsigned int)std::min<uint64_t>(c->cap2, 0xffffffffull), s.large_count);
+        // The first pass's argument blocks, with what differs: the redo's own cursors and regions, the gate, no next layout.
+        LayoutArgs lay{};
+        lay.s = bs; lay.m = m; lay.from = k1.bin; lay.next = {s.redo_cursors, s.redo_layout};
+        lay.key_entries = c->fc.bucket_cap; lay.spare_max = c->region_spare; lay.redo_gate = f.d_st;
+        launch_layout(lay);
+        k1.fc.redo_only = 1; k1.bin = lay.next;
+        launch_preprocess(k1); launch_bin_large(k1);
+        scan.bin = k1.bin; scan.next = {}; scan.redo_only = true;
+        launch_scan(scan);
     }
-    HIP_TRY(c, mark(2, bs));
-    if (ss != bs) {
-        HIP_TRY(c, hipEventRecord(s.ev_binned, bs));
+    HIP_TRY(c, f.mark(2, bs));
+    return SPLAT_OK;
+}
+
+// THE ORDERING STAGE, on f.ss behind the binning: the emit of two-pass binning, then the near selection or the sort launches.
+int order_frame(splat_ctx* c, const FrameLaunch& f) {
+    Slot& s = *f.s;
+    const splat_policy_decision& pd = f.pd;
+    hipStream_t ss = f.ss;
+    const unsigned int m = c->n_tiles;
+    if (ss != f.bs) {
+        HIP_TRY(c, hipEventRecord(s.ev_binned, f.bs));
         HIP_TRY(c, hipStreamWaitEvent(ss, s.ev_binned, 0));
     }
-    HIP_TRY(c, mark(8, ss));
-    if (!c->fc.bucket_cap)      // one-pass binning placed the keys in K1
-        launch_emit(ss, c->n, c->fc, s.depth, s.rect, c->orig, s.vislist, s.cursor, s.keys, d_st);
-    HIP_TRY(c, mark(3, ss));
-    const bool comp_sorts = comp_sorts_frame;
-    if (near_cap) {     // near selection: the nearest keys of the long lists instead of the sort launches
+    HIP_TRY(c, f.mark(8, ss));
+    if (!c->fc.bucket_cap) {    // one-pass binning placed the keys in K1
+        EmitArgs emit{};
+        emit.s = ss; emit.scene = scene_of(c); emit.fc = c->fc; emit.depth = s.depth; emit.rect = s.rect; emit.vislist = s.vislist;
+        emit.cursor = s.cursor; emit.keys = s.keys; emit.status = f.d_st;
+        launch_emit(emit);
+    }
+    HIP_TRY(c, f.mark(3, ss));
+    if (pd.near_cap) {     // near selection: the nearest keys of the long lists instead of the sort launches
         // Its workgroups: an eighth as many as tiles, each walking the longest-first order with that stride until the lists get
         // short -- a frame in the pipeline has 0.3 ms of slack in front of its compositor, and fewer resident selections leave
         // the previous frame's compositor its LDS (C3 +2 %, C3s +4 %; a sixteenth: C3 +1 %, C3s -1 %; a 64th: -15 %).  A frame
         // the caller waits for gets a workgroup per long list (their number a frame ago, plus an eighth).
-        launch_select(ss, m, s.offsets, s.order, s.lens, s.keys, s.keys2, d_st, c->orig, near_cap, c->need_hint, s.near_m,
-                      (unsigned int)c->fc.tiles_x, (unsigned int)c->fc.n_tile_rows, c->one_pass_select ? c->need_hint + 4u * (size_t)c->m_alloc : nullptr,
-                      pd.select_grid, c->fc.start_hints == 1, off2, pd.hint_radius);
+        const HintTable hints = hint_table(c);
+        SelectArgs sel{};
+        sel.s = ss; sel.knobs = &c->knobs; sel.n_tiles = m; sel.lists = f.lists; sel.keys = f.keys; sel.status = f.d_st; sel.orig = c->orig;
+        sel.near_cap = pd.near_cap; sel.need_hint = hints.needs(); sel.near_thr = c->one_pass_select ? hints.select_depth() : nullptr;
+        sel.tiles_x = (unsigned int)c->fc.tiles_x; sel.tile_rows = (unsigned int)c->fc.n_tile_rows;
+        sel.grid = pd.select_grid; sel.at_rest = c->fc.start_hints == 1; sel.hint_radius = pd.hint_radius;
+        launch_select(sel);
     }
-    else if (!comp_sorts)
-        launch_sort(ss, m, c->grid_big, c->grid_mid, c->grid_long, s.offsets, s.order, s.lens, s.keys, s.keys2, d_st, c->orig, c->fused_sort_max, off2);
-    HIP_TRY(c, mark(4, ss));
-    // Which lane composites?  Frames to one image stay on one lane (stream order is their write-after-write / in-out
-    // order, as always); a frame to another image takes the other lane when it may.  A frame that must not overlap
-    // (synchronous, statistics, overlap off) goes to lane 0 behind everything lane 1 still holds.
+    else if (pd.comp_sorts == 0) {
+        SortArgs sort{};
+        sort.s = ss; sort.knobs = &c->knobs; sort.n_tiles = m; sort.grids = {c->grid_big, c->grid_mid, c->grid_long};
+        sort.lists = f.lists; sort.keys = f.keys; sort.status = f.d_st; sort.orig = c->orig; sort.fused_sort_max = c->fused_sort_max;
+        launch_sort(sort);
+    }
+    HIP_TRY(c, f.mark(4, ss));
+    return SPLAT_OK;
+}
+
+// Which lane composites?  Frames to one image stay on one lane (stream order is their write-after-write / in-out
+// order, as always); a frame to another image takes the other lane when it may.  A frame that must not overlap
+// (synchronous, statistics, overlap off) goes to lane 0 behind everything lane 1 still holds.
+// Enqueues the waits the choice needs, enters the frame into the image table; *lane = 0 or 1.
+int pick_lane(splat_ctx* c, const char* img_lo, const char* img_hi, bool may_overlap, int ring_entry, int* lane) {
     int li = 0;
-    const char* const img_lo = reinterpret_cast<const char*>(d_argb);
-    const char* const img_hi = img_lo + (size_t)c->fc.W * (size_t)c->fc.H * 4u;
-    if (c->comp2) {
-        auto touches = [&](const splat_ctx::ImgRec& e) { return e.seq != 0 && img_lo < e.hi && e.lo < img_hi; };
-        const splat_ctx::ImgRec* newest = nullptr;        // the most recent frame to (a part of) this image
-        for (const auto& e : c->img_tab)
-            if (touches(e) && (!newest || e.seq > newest->seq)) newest = &e;
-        if (!may_overlap) li = 0;
-        else if (newest) li = newest->lane;
-        else li = c->lane[0].seq <= c->lane[1].seq ? 0 : 1;            // an image nobody holds: the lane idle for longer
-        hipStream_t mine = li ? c->comp2 : c->stream;
-        // Frames to this image on the OTHER lane come first.  (Ring events: when the ring wraps onto an entry the host
-        // has waited for that frame -- harvest -- so a re-recorded event only ever stands for a LATER frame.)
-        for (const auto& e : c->img_tab)
-            if (touches(e) && e.lane != li && e.ring >= 0) HIP_TRY(c, hipStreamWaitEvent(mine, c->ring[e.ring].e[7], 0));
-        if (!may_overlap && li == 0 && c->lane[1].seq != 0 && c->lane[1].ring >= 0)
-            HIP_TRY(c, hipStreamWaitEvent(mine, c->ring[c->lane[1].ring].e[7], 0));
-        // this frame's entry: the image's own one, else a free one, else the oldest -- whose frame this one then follows
-        // (an image that drops out of the table must not be in flight any more)
-        splat_ctx::ImgRec* slot = nullptr;
-        for (auto& e : c->img_tab) if (e.seq != 0 && e.lo == img_lo && e.hi == img_hi) { slot = &e; break; }
-        if (!slot) for (auto& e : c->img_tab) if (e.seq == 0) { slot = &e; break; }
-        if (!slot) {
-            for (auto& e : c->img_tab) if (!slot || e.seq < slot->seq) slot = &e;
-            if (slot->ring >= 0) {      // (both lanes: whichever lane the forgotten image's next frame takes, it follows)
-                HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ring[slot->ring].e[7], 0));
-                HIP_TRY(c, hipStreamWaitEvent(c->comp2, c->ring[slot->ring].e[7], 0));
-            }
+    *lane = 0;
+    if (!c->comp2) return SPLAT_OK;
+    auto touches = [&](const splat_ctx::ImgRec& e) { return e.seq != 0 && img_lo < e.hi && e.lo < img_hi; };
+    const splat_ctx::ImgRec* newest = nullptr;        // the most recent frame to (a part of) this image
+    for (const auto& e : c->img_tab)
+        if (touches(e) && (!newest || e.seq > newest->seq)) newest = &e;
+    if (!may_overlap) li = 0;
+    else if (newest) li = newest->lane;
+    else li = c->lane[0].seq <= c->lane[1].seq ? 0 : 1;            // an image nobody holds: the lane idle for longer
+    hipStream_t mine = li ? c->comp2 : c->stream;
+    // Frames to this image on the OTHER lane come first.  (Ring events: when the ring wraps onto an entry the host
+    // has waited for that frame -- harvest -- so a re-recorded event only ever stands for a LATER frame.)
+    for (const auto& e : c->img_tab)
+        if (touches(e) && e.lane != li && e.ring >= 0) HIP_TRY(c, hipStreamWaitEvent(mine, c->ring[e.ring].e[7], 0));
+    if (!may_overlap && li == 0 && c->lane[1].seq != 0 && c->lane[1].ring >= 0)
+        HIP_TRY(c, hipStreamWaitEvent(mine, c->ring[c->lane[1].ring].e[7], 0));
+    // this frame's entry: the image's own one, else a free one, else the oldest -- whose frame this one then follows
+    // (an image that drops out of the table must not be in flight any more)
+    splat_ctx::ImgRec* slot = nullptr;
+    for (auto& e : c->img_tab) if (e.seq != 0 && e.lo == img_lo && e.hi == img_hi) { slot = &e; break; }
+    if (!slot) for (auto& e : c->img_tab) if (e.seq == 0) { slot = &e; break; }
+    if (!slot) {
+        for (auto& e : c->img_tab) if (!slot || e.seq < slot->seq) slot = &e;
+        if (slot->ring >= 0) {      // (both lanes: whichever lane the forgotten image's next frame takes, it follows)
+            HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ring[slot->ring].e[7], 0));
+            HIP_TRY(c, hipStreamWaitEvent(c->comp2, c->ring[slot->ring].e[7], 0));
         }
-        slot->lo = img_lo; slot->hi = img_hi; slot->seq = c->lane_seq + 1; slot->ring = r; slot->lane = li;
     }
-    hipStream_t cs = li ? c->comp2 : c->stream;
+    slot->lo = img_lo; slot->hi = img_hi; slot->seq = c->lane_seq + 1; slot->ring = ring_entry; slot->lane = li;
+    *lane = li;
+    return SPLAT_OK;
+}
+
+// THE COMPOSITOR STAGE, on f.cs behind the ordering: the iteration buffer of a statistics frame, the launch, the late status, and
+// the ring event that says the frame has ended.
+int composite_frame(splat_ctx* c, const FrameLaunch& f, uint32_t* d_argb, bool want_iters) {
+    Slot& s = *f.s;
+    const splat_policy_decision& pd = f.pd;
+    hipStream_t cs = f.cs;
+    const unsigned int m = c->n_tiles;
     if (c->pre_wait) { HIP_TRY(c, hipStreamWaitEvent(cs, c->pre_wait, 0)); c->pre_wait = nullptr; }
-    if (c->pipeline && ss != cs) {
-        HIP_TRY(c, hipEventRecord(s.ev_ready, ss));
+    if (c->pipeline && f.ss != cs) {
+        HIP_TRY(c, hipEventRecord(s.ev_ready, f.ss));
         HIP_TRY(c, hipStreamWaitEvent(cs, s.ev_ready, 0));
     }
-    HIP_TRY(c, mark(5, cs));
+    HIP_TRY(c, f.mark(5, cs));
     uint2* iters = nullptr;
     c->iters_valid = false;
     if (want_iters) {       // statistics frame: every compositor wave leaves its iteration counts (plain stores)
@@ -918,20 +939,85 @@ int enqueue_frame(splat_ctx* c, uint32_t* d_argb, bool timed, bool want_iters = 
         iters = c->d_iters;
         c->iters_valid = true;
     }
+    CompositeArgs comp{};
+    comp.s = cs; comp.knobs = &c->knobs; comp.n_tiles = m; comp.fc = c->fc; comp.recs = s.recs; comp.argb = d_argb; comp.status = f.d_st; comp.orig = c->orig;
+    comp.fused_sort_max = c->fused_sort_max; comp.iters = iters; comp.keep_keys = want_iters;
     // throughput-bound frames (many pairs per key of the longest list: C3 737, C5 3100) keep the one-record walk, the
     // others (C2 316, an eighth-of-a-frame slab 92, C1 36) take the paired one; measured crossover between 316 and 737
-    const bool pair_walk = pd.pair_walk != 0;
-    launch_composite(cs, m, c->fc, s.offsets, s.order, s.lens, s.keys, s.recs, d_argb, d_st, c->orig, c->fused_sort_max, iters, want_iters,
-                     pair_walk, (c->cfg.mode & SPLAT_MODE_LIBM_EXP) != 0, c->clear_first, comp_sorts ? s.keys2 : nullptr, near_cap ? s.near_m : nullptr,
-                     c->need_hint, c->need_hint ? c->need_hint + 5u * (size_t)c->m_alloc : nullptr, off2,
-                     c->need_hint ? c->need_hint + 9u * (size_t)c->m_alloc : nullptr,
-                     c->fc.close_width == 0.0f ? pd.refine : 0u);      // (exact modes only: a fast-mode frame depends on where its walks start)
-    c->last_near = near_cap != 0u;
-    HIP_TRY(c, mark(6, cs));
+    comp.pair_walk = pd.pair_walk != 0;
+    comp.libm_exp = (c->cfg.mode & SPLAT_MODE_LIBM_EXP) != 0; comp.clear_first = c->clear_first;
+    // the frame's lists and key buffers, with what the compositor reads a meaning into: the second buffer only where it
+    // orders the long lists itself, the selections' lengths only where launch_select ran
+    comp.lists = f.lists; comp.lists.near_m = pd.near_cap ? s.near_m : nullptr;
+    comp.keys = f.keys; comp.keys.keys2 = pd.comp_sorts != 0 ? s.keys2 : nullptr;
+    comp.hints = hint_table(c);
+    comp.refine = c->fc.close_width == 0.0f ? pd.refine : 0u;      // (exact modes only: a fast-mode frame depends on where its walks start)
+    launch_composite(comp);
+    c->last_near = pd.near_cap != 0u;
+    HIP_TRY(c, f.mark(6, cs));
     // the scan has already delivered this frame's status to h_status[r]; a statistics frame refreshes it with the late
     // counters (compositor retries, sort fallbacks)
-    if (want_iters) HIP_TRY(c, hipMemcpyAsync(&c->h_status[r], d_st, sizeof(FrameStatus), hipMemcpyDeviceToHost, cs));
-    HIP_TRY(c, hipEventRecord(ev.e[7], cs));
+    if (want_iters) HIP_TRY(c, hipMemcpyAsync(&c->h_status[f.r], f.d_st, sizeof(FrameStatus), hipMemcpyDeviceToHost, cs));
+    HIP_TRY(c, hipEventRecord(f.ev->e[7], cs));
+    return SPLAT_OK;
+}
+
+// Enqueue one frame.  Never blocks the host unless the event ring wraps onto a frame that is
+// still running (32 frames behind).
+// `timed`: record the per-kernel timing events.  Every hipEventRecord is a barrier packet that
+// drains its queue for a few microseconds -- nine of them per frame were ~25 us of bubbles in a
+// 590 us frame -- so untimed frames (all but every `timing_every`-th of an asynchronous run) record
+// only the one event that tells the host the frame's status has arrived.
+// The stages: the frame's decisions (splat_policy_decide), bin_frame, order_frame, pick_lane, composite_frame.
+int enqueue_frame(splat_ctx* c, uint32_t* d_argb, bool timed, bool want_iters = false, bool may_overlap = false, bool awaited = false) {
+    FrameLaunch f{};
+    const int r = c->ring_next;
+    EvSet& ev = c->ring[r];
+    f.r = r; f.ev = &ev; f.timed = timed;
+    c->ring_next = (c->ring_next + 1) % EV_RING;
+    harvest(c, r);
+    std::memset(&c->h_status[r], 0, sizeof(FrameStatus));      // (this frame's scan fills it; until then it says nothing: see the peek below)
+    const int si = (int)(c->frame_idx++ % (uint64_t)slots_in_use(c));
+    Slot& s = c->slots[si];
+    f.si = si; f.s = &s; f.d_st = c->d_status_ring + r;       // (initialised by this frame's scan)
+    // pipeline depth 1: everything on the caller's stream.  2: K1..K3 of frame N+1 on the bin stream
+    // under the compositor of frame N.  3: K1 + scan of frame N+2 on the bin stream, K2 + K3 of
+    // frame N+1 on the sort stream, compositor of frame N on the caller's stream -- the bin chain is
+    // the longest of the three under contention, so splitting it raises the frame rate.
+    f.bs = c->pipeline ? c->bin_stream : c->stream;
+    // 6 (default): four slots, and the bin + sort chains of consecutive frames alternate between two streams, so
+    // the chain of frame N+2 (a latency chain: K1 -> scan -> sort) runs beside the chain of frame N+1 and the
+    // compositor of frame N.  With one chain at a time the frame time IS the chain's length under contention
+    // (C3: 0.28 + 0.03 + 0.11 = 0.42 ms against a compositor of 0.37); two in flight leave the compositor as the
+    // bound: C3 2241 -> 2334 fps, C1 17.4 k -> 19.2 k, C5 +1 %, C2 -1 %
+    if (c->pipeline >= 6 && (c->frame_idx & 1ull)) f.bs = c->sort_stream;
+    f.ss = c->pipeline == 3 ? c->sort_stream : f.bs;     // (4, 5: three / four slots on two streams)
+    // THE FRAME'S DECISIONS (include/splat_policy.h): everything below this call only launches what it says.
+    {
+        const splat_policy_knobs pk = policy_knobs_of(c);
+        const splat_policy_input pi = policy_input_of(c, s, r, awaited);
+        if (splat_policy_decide(&pk, &c->pol, &pi, &f.pd) != 0) return fail(c, SPLAT_ERR_INVALID, "frame policy refused its input");
+        c->pol = f.pd.next;
+    }
+    // A frame the caller waits for, with nothing else in flight (the reference's loop: one synchronous frame per pose,
+    // src/main.rs:69-78), has nothing to overlap with: its whole chain goes on the caller's stream, in order (pd.solo) -- no
+    // event recorded on one stream and waited for on another between its binning and its compositor (two barrier packets and
+    // a cross-queue hand-over: ~15 us of a 0.6-ms frame).
+    if (f.pd.solo != 0) { f.bs = c->stream; f.ss = c->stream; }
+    c->idle = false;
+    // (two-pass binning: the second buffer mirrors the first)
+    f.lists = {s.offsets, s.order, s.lens, s.cursor, c->fc.bucket_cap ? s.off2 : nullptr, s.near_m};
+    f.keys = {s.keys, s.keys2, c->cap, (unsigned int)std::min<uint64_t>(c->cap2, 0xffffffffull)};
+    int rc = bin_frame(c, f);
+    if (rc == SPLAT_OK) rc = order_frame(c, f);
+    if (rc != SPLAT_OK) return rc;
+    int li = 0;
+    const char* const img_lo = reinterpret_cast<const char*>(d_argb);
+    rc = pick_lane(c, img_lo, img_lo + (size_t)c->fc.W * (size_t)c->fc.H * 4u, may_overlap, r, &li);
+    if (rc != SPLAT_OK) return rc;
+    f.cs = li ? c->comp2 : c->stream;
+    rc = composite_frame(c, f, d_argb, want_iters);
+    if (rc != SPLAT_OK) return rc;
     s.free_ring = r;
     HIP_TRY(c, hipGetLastError());
     s.used = true;
@@ -1039,7 +1125,7 @@ int prepare_binning(splat_ctx* c, unsigned int m, FrameConst* fc) {
             sl.layout_valid = false; sl.flip = 0;
             if (sl.counts) HIP_TRY(c, hipMemsetAsync(sl.counts, 0, sizeof(unsigned int) * (size_t)(m + 1), c->stream));
         }
-        if (c->need_hint) HIP_TRY(c, hipMemsetAsync(c->need_hint, 0, sizeof(unsigned int) * HINT_WORDS * (size_t)c->m_alloc, c->stream));   // another grid: another tile under every index
+        if (c->need_hint) HIP_TRY(c, hipMemsetAsync(c->need_hint, 0, hint_table(c).bytes(), c->stream));   // another grid: another tile under every index
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         c->last_one_pass = one_pass; c->layout_m = m;
         reset_policy(c);
@@ -1480,7 +1566,7 @@ int splat_set_option(splat_ctx* c, int32_t option, double value) {
     if (!store_option(c, option, value)) return fail(c, SPLAT_ERR_INVALID, "option value out of range");
     // (another selection size: what the tiles' walks needed under the old one is forgotten)
     if (option == SPLAT_OPT_NEAR_SELECT_KEYS && c->need_hint && c->m_alloc)
-        HIP_TRY(c, fill_now(c->need_hint, 0, sizeof(unsigned int) * HINT_WORDS * (size_t)c->m_alloc));
+        HIP_TRY(c, fill_now(c->need_hint, 0, hint_table(c).bytes()));
     // (the large list switched on with a scene in place: its buffers exist from now on -- splat_upload_scene makes them otherwise)
     if (option == SPLAT_OPT_LARGE_SPLAT_TILES && c->large_tiles >= 0 && c->n != 0)
         for (Slot& sl : c->slots)
@@ -1547,7 +1633,7 @@ void upload_finish(splat_ctx* c, uint64_t n) {
     for (Slot& sl : c->slots) sl.layout_valid = false;
     c->sort_hint = false;
     // another scene under every tile: what the walks of the old one needed says nothing (near selection, start hints)
-    if (c->need_hint && c->m_alloc) (void)fill_now(c->need_hint, 0, sizeof(unsigned int) * HINT_WORDS * (size_t)c->m_alloc);
+    if (c->need_hint && c->m_alloc) (void)fill_now(c->need_hint, 0, hint_table(c).bytes());
     reset_policy(c);
     // The per-tile arrays (a few hundred KB per frame slot at 4K) exist before the first frame as well: fifty small allocations
     // and six synchronous fills were a third of its call.  A larger target than 3840 x 2160 makes them again, as always.
@@ -1584,6 +1670,13 @@ hipError_t follow_producer(splat_ctx* c, void* producer) {
 
 extern "C" {
 
+// the two uploads' HIP calls: a failure releases the upload's temporaries (`cleanup`) and reports the call (`e`: a local)
+#define UP_TRY(expr)                                                            \
+    if ((e = (expr)) != hipSuccess) {                                            \
+        cleanup();                                                               \
+        return fail(c, SPLAT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e)); \
+    }
+
 int splat_upload_scene(splat_ctx* c, uint64_t n, const float* pos4, const float* cov3d, const float* opacity,
                        const float* sh) {
     if (!c) return SPLAT_ERR_INVALID;
@@ -1596,11 +1689,6 @@ int splat_upload_scene(splat_ctx* c, uint64_t n, const float* pos4, const float*
     float *d_pos = nullptr, *d_cov = nullptr, *d_op = nullptr, *d_sh = nullptr;
     auto cleanup = [&] { dfree(d_pos); dfree(d_cov); dfree(d_op); dfree(d_sh); };
     hipError_t e;
-#define UP_TRY(expr)                                                            \
-    if ((e = (expr)) != hipSuccess) {                                            \
-        cleanup();                                                               \
-        return fail(c, SPLAT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e)); \
-    }
     UP_TRY(alloc_scene(c, n));
     UP_TRY(hipMemcpyAsync(c->orig, c->h_orig.data(), sizeof(unsigned int) * n, hipMemcpyHostToDevice, c->stream));
     std::vector<BlockBounds> hb;
@@ -1618,7 +1706,6 @@ int splat_upload_scene(splat_ctx* c, uint64_t n, const float* pos4, const float*
     launch_pack_scene(c->stream, n, d_pos, d_cov, d_op, d_sh, c->orig, c->planes);
     UP_TRY(hipGetLastError());
     UP_TRY(hipStreamSynchronize(c->stream));
-#undef UP_TRY
     cleanup();
     upload_finish(c, n);
     return SPLAT_OK;
@@ -1638,11 +1725,6 @@ int splat_upload_scene_device(splat_ctx* c, uint64_t n, const void* d_pos4, cons
     hipEvent_t ev[2] = {nullptr, nullptr};
     auto cleanup = [&] { dfree(d_sort); dfree(d_small); for (hipEvent_t& x : ev) if (x) { (void)hipEventDestroy(x); x = nullptr; } };
     hipError_t e;
-#define UP_TRY(expr)                                                            \
-    if ((e = (expr)) != hipSuccess) {                                            \
-        cleanup();                                                               \
-        return fail(c, SPLAT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e)); \
-    }
     UP_TRY(alloc_scene(c, n));
     UP_TRY(dmalloc(c, &c->bounds, sizeof(BlockBounds) * ((n + 255) / 256)));
     UP_TRY(dmalloc(c, &d_sort, sizeof(uint32_t) * 4 * n));
@@ -1736,7 +1818,7 @@ int splat_set_slab(splat_ctx* c, int32_t tile_row0, int32_t tile_row1) {
     for (Slot& sl : c->slots) sl.layout_valid = false;
     c->sort_hint = false;
     c->hint_pairs = 0; c->hint_maxlen = 0;
-    if (c->need_hint && c->m_alloc) (void)hipMemsetAsync(c->need_hint, 0, sizeof(unsigned int) * HINT_WORDS * (size_t)c->m_alloc, c->stream);
+    if (c->need_hint && c->m_alloc) (void)hipMemsetAsync(c->need_hint, 0, hint_table(c).bytes(), c->stream);
     c->slab0 = tile_row0; c->slab1 = tile_row1;
     reset_policy(c);
     return rc;
@@ -1766,8 +1848,14 @@ int splat_tile_row_loads(splat_ctx* c, const splat_camera* cam, uint64_t* row_pa
     HIP_TRY(c, hipMemsetAsync(s.counts, 0, sizeof(unsigned int) * ((size_t)nt + 1), c->stream));   // (one-pass frames leave cursors there)
     s.layout_valid = false; s.flip = 0;                                                          // ... and will find them gone
     HIP_TRY(c, hipMemsetAsync(s.d_status, 0, sizeof(FrameStatus), c->stream));
-    launch_preprocess(c->stream, c->n, c->planes, c->orig, fc, s.recs, s.depth, s.rect, s.counts, s.vislist, nullptr, c->bounds, s.blockinfo, s.d_status);
-    launch_scan(c->stream, nt, s.counts, s.offsets, s.cursor, s.order, s.lens, s.d_status, ~0ull, 0u, nt, nt, nt);
+    BinArgs k1{};       // (the counting flavour: no layout, no keys)
+    k1.s = c->stream; k1.knobs = &c->knobs; k1.scene = scene_of(c); k1.fc = fc; k1.recs = s.recs; k1.depth = s.depth; k1.rect = s.rect; k1.vislist = s.vislist;
+    k1.bin.cursors = s.counts; k1.blockinfo = s.blockinfo; k1.status = s.d_status;
+    launch_preprocess(k1);
+    ScanArgs scan{};
+    scan.s = c->stream; scan.knobs = &c->knobs; scan.m = nt; scan.bin = k1.bin; scan.lists = {s.offsets, s.order, s.lens, s.cursor, nullptr, nullptr};
+    scan.keys.cap = ~0ull; scan.grids = {nt, nt, nt}; scan.status = s.d_status;
+    launch_scan(scan);
     HIP_TRY(c, hipGetLastError());
     std::vector<unsigned int> off((size_t)nt + 1);
     HIP_TRY(c, hipMemcpyAsync(off.data(), s.offsets, sizeof(unsigned int) * off.size(), hipMemcpyDeviceToHost, c->stream));
@@ -1784,23 +1872,7 @@ namespace {
 // host_out != nullptr (splat_render_frame): the rendered rows also travel to host memory behind the compositor, on its stream,
 // BEFORE the host waits -- one wait per frame; a frame the device skipped is redone and copied again
 int render_device_impl(splat_ctx* c, const splat_camera* cam, void* d_argb, int32_t sync, splat_stats* stats, bool clear_first,
-                       uint32_t* host_out = nullptr);
-}
-
-extern "C" {
-
-int splat_render_device(splat_ctx* c, const splat_camera* cam, void* d_argb, int32_t sync, splat_stats* stats) {
-    return render_device_impl(c, cam, d_argb, sync, stats, false);
-}
-int splat_render_frame_device(splat_ctx* c, const splat_camera* cam, void* d_argb, int32_t sync, splat_stats* stats) {
-    return render_device_impl(c, cam, d_argb, sync, stats, true);
-}
-
-}  // extern "C"
-
-namespace {
-int render_device_impl(splat_ctx* c, const splat_camera* cam, void* d_argb, int32_t sync, splat_stats* stats, bool clear_first,
-                       uint32_t* host_out) {
+                       uint32_t* host_out = nullptr) {
     if (!c) return SPLAT_ERR_INVALID;
     if (!d_argb) return fail(c, SPLAT_ERR_INVALID, "d_argb is NULL");
     HIP_TRY(c, hipSetDevice(c->cfg.device));
@@ -1865,6 +1937,13 @@ int render_device_impl(splat_ctx* c, const splat_camera* cam, void* d_argb, int3
 }  // namespace
 
 extern "C" {
+
+int splat_render_device(splat_ctx* c, const splat_camera* cam, void* d_argb, int32_t sync, splat_stats* stats) {
+    return render_device_impl(c, cam, d_argb, sync, stats, false);
+}
+int splat_render_frame_device(splat_ctx* c, const splat_camera* cam, void* d_argb, int32_t sync, splat_stats* stats) {
+    return render_device_impl(c, cam, d_argb, sync, stats, true);
+}
 
 int splat_render(splat_ctx* c, const splat_camera* cam, uint32_t* argb, splat_stats* stats) {
     if (!c) return SPLAT_ERR_INVALID;
@@ -2106,7 +2185,10 @@ int splat_get_records(splat_ctx* c, splat_record* out, uint64_t n) {
         HIP_TRY(c, hipMemsetAsync(sl.counts, 0, sizeof(unsigned int) * ((size_t)c->n_tiles + 1), c->stream));   // (cursors of a one-pass frame)
         sl.layout_valid = false; sl.flip = 0;
         HIP_TRY(c, hipMemsetAsync(s.d_status, 0, sizeof(FrameStatus), c->stream));
-        launch_preprocess(c->stream, c->n, c->planes, c->orig, fc, s.recs, s.depth, s.rect, s.counts, s.vislist, nullptr, nullptr, nullptr, s.d_status);
+        BinArgs k1{};       // (no bounds, no block words, no layout, no keys)
+        k1.s = c->stream; k1.knobs = &c->knobs; k1.scene = {c->n, c->planes, c->orig, nullptr}; k1.fc = fc; k1.recs = s.recs; k1.depth = s.depth; k1.rect = s.rect;
+        k1.vislist = s.vislist; k1.bin.cursors = s.counts; k1.status = s.d_status;
+        launch_preprocess(k1);
         HIP_TRY(c, hipMemsetAsync(s.counts, 0, sizeof(unsigned int) * ((size_t)c->n_tiles + 1), c->stream));
         HIP_TRY(c, hipMemsetAsync(s.d_status, 0, sizeof(FrameStatus), c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -2146,7 +2228,7 @@ int splat_debug_near_state(splat_ctx* c, unsigned int* lens, unsigned int* near_
     const Slot& s = c->slots[c->last_slot];
     bool ok = hipMemcpy(lens, s.lens, sizeof(unsigned int) * m, hipMemcpyDeviceToHost) == hipSuccess;
     ok = ok && hipMemcpy(near_m, s.near_m, sizeof(unsigned int) * m, hipMemcpyDeviceToHost) == hipSuccess;
-    ok = ok && hipMemcpy(need_hint, c->need_hint, sizeof(unsigned int) * 4u * m, hipMemcpyDeviceToHost) == hipSuccess;
+    ok = ok && hipMemcpy(need_hint, hint_table(c).needs(), sizeof(unsigned int) * HintTable::NEED_PLANES * m, hipMemcpyDeviceToHost) == hipSuccess;
     return ok ? SPLAT_OK : SPLAT_ERR_HIP;
 }
 
@@ -2176,9 +2258,11 @@ int splat_get_tile_lists(splat_ctx* c, uint32_t* tile_offsets, uint64_t n_offset
     if (c->last_near && c->last.overflow == 0) {
         // the frame's compositor selected the nearest keys of every list of more than 2048 keys and left the list itself
         // as K1 had written it: put those lists in order now (the sort launches, every tile in their grids)
-        use_launch_knobs(&c->knobs);
-        launch_sort(c->stream, c->n_tiles, c->n_tiles, c->n_tiles, c->n_tiles, s.offsets, s.order, s.lens, s.keys, s.keys2, c->slots[c->last_slot].d_status, c->orig, 2048u,
-                    c->fc.bucket_cap ? s.off2 : nullptr);
+        SortArgs sort{};
+        sort.s = c->stream; sort.knobs = &c->knobs; sort.n_tiles = c->n_tiles; sort.grids = {c->n_tiles, c->n_tiles, c->n_tiles};
+        sort.lists = {s.offsets, s.order, s.lens, s.cursor, c->fc.bucket_cap ? s.off2 : nullptr, s.near_m};
+        sort.keys.keys = s.keys; sort.keys.keys2 = s.keys2; sort.status = s.d_status; sort.orig = c->orig; sort.fused_sort_max = 2048u;
+        launch_sort(sort);
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         c->last_near = false;

@@ -104,7 +104,8 @@ struct Rec {
 };
 
 // Experiment switches of the launch wrappers (SPLAT_SORT_RADIX_MIN, SPLAT_SCAN_THREADS, SPLAT_DBG_NTILES, SPLAT_COMP_LDS_PAD):
-// per context, read at splat_create; use_launch_knobs() makes a context's set current for the calling thread.
+// per context, read from the environment at splat_create.  They travel with every launch: each argument block below that needs
+// them points at the launching context's set.
 struct LaunchKnobs {
     unsigned int sort_radix_min = 128;     // lists up to this length use the bitonic network
     int scan_threads = 0;                  // 0: by the tile count
@@ -116,12 +117,33 @@ struct LaunchKnobs {
     int dbg_hint_radius = -1;              // SPLAT_DBG_HINT_RADIUS: the near selection's neighbourhood, in tiles (default: by the camera's motion)
     unsigned int dbg_starts = 0;           // SPLAT_DBG_STARTS: statistics frames record (list length, nearest keys the walk needed) per wave
 };
-void use_launch_knobs(const LaunchKnobs* k);
+
+// The per-tile hint table, kept from frame to frame: ONE allocation of HINT_WORDS planes of `stride` words (the context's
+// m_alloc).  A part of P planes holds P words per tile, tile after tile.  This is the only place that knows where the parts are.
+struct HintTable {
+    unsigned int* base;     // nullptr: no table (every part is nullptr then)
+    size_t stride;          // words per plane
+
+    static constexpr unsigned int NEED_PLANE = 0u, NEED_PLANES = 4u;                                   // per wave: the nearest keys of the list its walk needed
+    static constexpr unsigned int DEPTH_PLANE = NEED_PLANE + NEED_PLANES, DEPTH_PLANES = 1u;           // the depth the tile's last near selection began at
+    static constexpr unsigned int START_PLANE = DEPTH_PLANE + DEPTH_PLANES, START_PLANES = 4u;         // per wave: where its exact walk started
+    static constexpr unsigned int REFINE_PLANE = START_PLANE + START_PLANES, REFINE_PLANES = 4u;       // per wave: the state of its start's refinement at rest
+    static constexpr unsigned int HINT_WORDS = 13u;                                                    // planes in all = words per tile
+    static_assert(DEPTH_PLANE == 4u && START_PLANE == 5u && REFINE_PLANE == 9u && REFINE_PLANE + REFINE_PLANES == HINT_WORDS,
+                  "the four parts tile the table exactly");
+
+    unsigned int* plane(unsigned int k) const { return base ? base + k * stride : nullptr; }
+    unsigned int* needs() const { return plane(NEED_PLANE); }
+    unsigned int* select_depth() const { return plane(DEPTH_PLANE); }
+    unsigned int* starts() const { return plane(START_PLANE); }
+    unsigned int* refinement() const { return plane(REFINE_PLANE); }
+    size_t words() const { return HINT_WORDS * stride; }
+    size_t bytes() const { return sizeof(unsigned int) * words(); }
+};
 
 void launch_pack_scene(hipStream_t s, uint64_t n, const float* pos4, const float* cov3d, const float* opacity,
                        const float* sh, const unsigned int* perm, float4* planes);
 void launch_cov3d(hipStream_t s, uint64_t n, const float* scales3, const float* rot4, float* cov3d);
-struct BlockBounds;
 // The scene's order on the device (splat_upload_scene_device): orig[j] = the Gaussian stored in slot j, as morton_order of
 // splat_api.hip orders them.  pingpong: 4 n words (the sort's two key and two index arrays); small:
 // scene_order_small_bytes(n) bytes (scan tables, partial boxes).  The two events, when given, are recorded around the sort.
@@ -130,84 +152,128 @@ void launch_scene_order(hipStream_t s, uint64_t n, const float* pos4, uint32_t* 
                         hipEvent_t sort_begin = nullptr, hipEvent_t sort_end = nullptr);
 // ... and the bounds of its K1 blocks, as block_bounds of splat_api.hip computes them
 void launch_block_bounds(hipStream_t s, uint64_t n, const float* pos4, const float* cov3d, const unsigned int* orig, BlockBounds* bounds);
-void launch_preprocess(hipStream_t s, uint64_t n, const float4* planes, const unsigned int* orig, FrameConst fc, Rec* recs,
-                       float* depth, ushort4* rect, unsigned int* counts, unsigned int* vislist, unsigned long long* keys,
-                       const BlockBounds* bounds,
-                       unsigned int* blockinfo /* per block: bit 31 = skipped by culling; one-pass binning: visible | singular << 9 */,
-                       FrameStatus* status,
-                       const unsigned int* layout = nullptr /* one-pass binning (fc.bucket_cap != 0): counts[t] is the cursor of tile t's
-                                                               region keys[layout[t] .. layout[t+1]); nullptr: two-pass counting */,
-                       bool count_only = false /* one-pass binning's COUNT flavour: counts[t] += the tile's pairs and nothing else (no SH,
-                                                  no record, no key) -- the pass in front of a layout that fits exactly this camera */,
-                       uint4* large_list = nullptr, unsigned int* large_count = nullptr /* one-pass binning: the frame's list of large
-                                                  splats (n entries) and its counter -- launch_bin_large behind this launch bins them */);
-// the large splats K1 listed, tile by tile (bin_large_kernel): same stream, right behind launch_preprocess; `cursors` as given to it
-void launch_bin_large(hipStream_t s, const FrameConst& fc, const uint4* large_list, const unsigned int* large_count, unsigned int large_cap, unsigned int* cursors,
-                      unsigned long long* keys, const FrameStatus* status, bool count_only);
-void launch_scan(hipStream_t s, unsigned int m, unsigned int* counts, unsigned int* offsets, unsigned int* cursor,
-                 unsigned int* order, unsigned int* lens, FrameStatus* status, unsigned long long capacity,
-                 unsigned int bucket_cap, unsigned int grid_big, unsigned int grid_mid, unsigned int grid_long,
-                 FrameStatus* host_status = nullptr /* pinned, device-visible: the scan also delivers the status there */,
-                 const unsigned int* layout = nullptr /* one-pass binning: the regions the frame was binned into */,
-                 unsigned int* next_layout = nullptr, unsigned int* next_counts = nullptr /* both given: a second workgroup of
-                     the launch builds the regions + cursors of the next frame on this stream (see launch_layout) */,
-                 float spare_max = 4.0f /* how far a region may grow into the buffer's spare room */,
-                 bool redo_only = false /* the second scan of a frame binned again on the device: nothing unless status->overflow == 2 */,
-                 unsigned int* off2 = nullptr /* one-pass binning: per tile, where its room in the SECOND key buffer starts -- handed out
-                                                 by this scan to the lists of more than 2048 keys */,
-                 unsigned int cap2 = 0 /* entries of the second key buffer: beyond it the frame is flagged (overflow 4) */,
-                 unsigned int* large_count = nullptr /* the frame's large-splat counter: reset here for the slot's next K1 */,
-                 unsigned int tiles_x = 0, unsigned int motion_radius = 0 /* != 0 (a moving camera): the next frame's regions are sized from
-                                                 the longest list within this many tiles of each tile (build_layout) */);
-// the regions (and cursors) of the slot's next one-pass frame from this frame's lists; an all-zero `layout` with cursors
+
+// ---- The per-frame launches take one argument block each, by const&.  The blocks are plain aggregates without defaults: a
+// caller value-initialises one (`ScanArgs a{};`) and what it does not set is zero / nullptr / false.  What travels together
+// is a sub-struct:
+struct SceneArgs {                  // the uploaded scene
+    uint64_t n;
+    const float4* planes;
+    const unsigned int* orig;       // slot -> original index: the order among equal depths
+    const BlockBounds* bounds;
+};
+struct TileLists {                  // a frame slot's tile lists
+    unsigned int *offsets, *order, *lens;   // per tile: where its list starts in keys; the tiles, longest list first; the lists' lengths
+    unsigned int* cursor;           // two-pass binning: the emit's cursors
+    unsigned int* off2;             // one-pass binning: per tile, where its room in the SECOND key buffer starts -- handed out by the scan to the
+                                    // lists of more than 2048 keys; nullptr: at offsets[tile], like its list in keys
+    unsigned int* near_m;           // near selection: per tile, how many of the nearest keys are in order
+};
+struct BinTarget {                  // what K1 bins into
+    unsigned int* cursors;          // per tile: pair count (two-pass counting) / cursor of the tile's region
+    unsigned int* layout;           // one-pass binning (fc.bucket_cap != 0): cursors[t] is the cursor of tile t's region
+                                    // keys[layout[t] .. layout[t+1]); nullptr: two-pass counting
+};
+struct KeyBuffers {
+    unsigned long long *keys, *keys2;   // keys2: sorted near selections, scatter space of the long lists' sorts and merges
+    unsigned long long cap;         // entries of keys: beyond it a two-pass frame is flagged (overflow 1)
+    unsigned int cap2;              // entries of keys2: beyond it the frame is flagged (overflow 4)
+};
+struct LargeList {                  // one-pass binning: the frame's list of large splats -- launch_bin_large behind K1 bins them
+    uint4* list;                    // nullptr with a counter: large splats are only counted
+    unsigned int* count;
+    unsigned int cap;               // entries of list
+};
+struct SortGrids { unsigned int big, mid, lng; };    // how many entries of `order` (longest lists first) the 1024-thread, the 512-thread and the
+                                                     // run-merging sort launches cover; the scan validates them against the frame's actual list lengths
+
+// K1, and behind it on the same stream the large splats it listed, tile by tile (bin_large_kernel): both take this block
+struct BinArgs {
+    hipStream_t s; const LaunchKnobs* knobs; SceneArgs scene; FrameConst fc;
+    Rec* recs; float* depth; ushort4* rect; unsigned int* vislist; unsigned long long* keys; FrameStatus* status;
+    BinTarget bin;
+    unsigned int* blockinfo;        // per block: bit 31 = skipped by culling; one-pass binning: visible | singular << 9
+    bool count_only;                // one-pass binning's COUNT flavour: cursors[t] += the tile's pairs and nothing else (no SH, no record,
+                                    // no key) -- the pass in front of a layout that fits exactly this camera
+    LargeList large;
+};
+void launch_preprocess(const BinArgs& a);
+void launch_bin_large(const BinArgs& a);
+
+struct NextRegions {                // the scan's second workgroup: with both of `to` given it builds the regions + cursors of the next frame on
+    BinTarget to;                   // this stream (see launch_layout)
+    unsigned int tiles_x, motion_radius;    // != 0 (a moving camera): those regions are sized from the longest list within this many tiles
+};                                          // of each tile (build_layout)
+struct ScanArgs {
+    hipStream_t s; const LaunchKnobs* knobs; unsigned int m;
+    BinTarget bin;                  // what the frame was binned into
+    TileLists lists; KeyBuffers keys; unsigned int bucket_cap; SortGrids grids; FrameStatus* status;
+    FrameStatus* host_status;       // pinned, device-visible: the scan also delivers the status there
+    NextRegions next;
+    float spare_max;                // how far a region may grow into the buffer's spare room
+    bool redo_only;                 // the second scan of a frame binned again on the device: nothing unless status->overflow == 2
+    unsigned int* large_count;      // the frame's large-splat counter: reset here for the slot's next K1
+};
+void launch_scan(const ScanArgs& a);
+
+// the regions (and cursors) of the slot's next one-pass frame from this frame's lists; an all-zero `from.layout` with cursors
 // counted from zero is the bootstrap
-void launch_layout(hipStream_t s, unsigned int m, const unsigned int* counts, const unsigned int* layout, unsigned int* next_layout,
-                   unsigned int* next_counts, unsigned int key_entries, FrameStatus* status, FrameStatus* host_status, float spare_max = 4.0f,
-                   const FrameStatus* redo_gate = nullptr /* != nullptr: a redo launch -- does nothing unless redo_gate->overflow == 2 */,
-                   unsigned int* large_count = nullptr /* see launch_scan */);
-void launch_emit(hipStream_t s, uint64_t n, FrameConst fc, const float* depth, const ushort4* rect, const unsigned int* orig,
-                 const unsigned int* vislist, unsigned int* cursor, unsigned long long* keys, const FrameStatus* status);
-// grid_big / grid_mid: how many entries of `order` (longest lists first) the 1024- and 512-thread
-// sort launches cover; the scan validates them against the frame's actual list lengths.
-void launch_sort(hipStream_t s, unsigned int n_tiles, unsigned int grid_big, unsigned int grid_mid, unsigned int grid_long, const unsigned int* offsets,
-                 const unsigned int* order, const unsigned int* lens, unsigned long long* keys, unsigned long long* keys2,
-                 FrameStatus* status, const unsigned int* orig /* slot -> original index: the order among equal depths */,
-                 unsigned int fused_sort_max = 0,
-                 const unsigned int* off2 = nullptr /* where a tile's room in keys2 starts; nullptr: at offsets[tile], like its list in keys */);
-// fused_sort_max: lists of up to this many keys (<= 2048) are sorted by the compositor's workgroups
-// themselves (launch_sort must be given the same value and then leaves them alone); 0 = off.
+struct LayoutArgs {
+    hipStream_t s; unsigned int m; BinTarget from, next; unsigned int key_entries; FrameStatus *status, *host_status; float spare_max;
+    const FrameStatus* redo_gate;   // != nullptr: a redo launch -- does nothing unless redo_gate->overflow == 2
+    unsigned int* large_count;      // see ScanArgs
+};
+void launch_layout(const LayoutArgs& a);
+
+struct EmitArgs {
+    hipStream_t s; SceneArgs scene; FrameConst fc; const float* depth; const ushort4* rect; const unsigned int* vislist;
+    unsigned int* cursor; unsigned long long* keys; const FrameStatus* status;
+};
+void launch_emit(const EmitArgs& a);
+
+struct SortArgs {
+    hipStream_t s; const LaunchKnobs* knobs; unsigned int n_tiles; SortGrids grids; TileLists lists; KeyBuffers keys; FrameStatus* status;
+    const unsigned int* orig;
+    unsigned int fused_sort_max;    // lists of up to this many keys (<= 2048) are sorted by the compositor's workgroups themselves
+                                    // (launch_composite must be given the same value; launch_sort then leaves them alone); 0 = off
+};
+void launch_sort(const SortArgs& a);
+
 // near selection instead of the sort launches: the nearest keys of every list of more than 2048 keys, by last frame's need
-void launch_select(hipStream_t s, unsigned int n_tiles, const unsigned int* offsets, const unsigned int* order, const unsigned int* lens,
-                   unsigned long long* keys, unsigned long long* keys2, FrameStatus* status, const unsigned int* orig, unsigned int near_cap,
-                   const unsigned int* need_hint, unsigned int* near_m /* per tile: how many of the nearest keys are in order */,
-                   unsigned int tiles_x, unsigned int tile_rows /* the tile grid: a tile's selection also looks at its neighbours' hints */,
-                   unsigned int* near_thr = nullptr /* one word per tile, kept from frame to frame: the depth its last selection began at */,
-                   unsigned int grid = 0 /* workgroups (each strides over the tile order); 0 = an eighth of the tiles */,
-                   bool at_rest = false /* the camera of the last frames: selections sized tightly */,
-                   const unsigned int* off2 = nullptr /* see launch_sort */,
-                   int hint_radius = 2 /* a tile's selection is sized from its own walks' need and its neighbours' within this many tiles */);
-void launch_composite(hipStream_t s, unsigned int n_tiles, FrameConst fc, const unsigned int* offsets,
-                      const unsigned int* order, const unsigned int* lens, unsigned long long* keys, const Rec* recs,
-                      uint32_t* argb, FrameStatus* status, const unsigned int* orig, unsigned int fused_sort_max = 0,
-                      uint2* iters = nullptr /* per wave (scan, blend) iteration counts, statistics frames only */,
-                      bool keep_keys = true /* lists sorted inside the compositor are also written back to the bucket
-                                               (the debug getters read them there); off on ordinary frames */,
-                      bool pair_walk = false /* the two-records-per-step flavour of the exact walk (same pixels) */,
-                      bool libm_exp = false /* SPLAT_MODE_LIBM_EXP: expf as the host libm computes it */,
-                      bool clear_first = false /* the frame starts from a cleared image: old pixels are not read, tiles
-                                                  nothing covers are zeroed (color.clear(0) of src/main.rs:73, fused) */,
-                      unsigned long long* keys2 = nullptr /* != nullptr: no sort launch ran; lists of more than 2048 keys
-                                                             are sorted by their tile's workgroup through this buffer */,
-                      const unsigned int* near_m = nullptr /* != nullptr (with keys2): near selection -- launch_select ran in front: of a
-                                                   list of more than 2048 keys only the nearest near_m[tile] are in order (composite_tile) */,
-                      unsigned int* need_hint = nullptr /* 4 words per tile, kept from frame to frame: how many of its list's nearest
-                                                           keys each wave's walk needed (sizes the next frame's selection) */,
-                      unsigned int* start_hint = nullptr /* 4 words per tile, kept from frame to frame: where each wave's exact walk
-                                                            started, in keys from the list's near end (fc.start_hints) */,
-                      const unsigned int* off2 = nullptr /* see launch_sort */,
-                      unsigned int* probe_hint = nullptr /* 4 words per tile beside start_hint, kept from frame to frame: each wave's
-                                                            start refinement at rest (composite_tile, phase A) */,
-                      unsigned int refine = 0u /* != 0: this frame's waves refine their starts (splat_policy_decision::refine) */);
+struct SelectArgs {
+    hipStream_t s; const LaunchKnobs* knobs; unsigned int n_tiles; TileLists lists; KeyBuffers keys; FrameStatus* status;
+    const unsigned int* orig;
+    unsigned int near_cap;
+    const unsigned int* need_hint;  // HintTable::needs()
+    unsigned int* near_thr;         // HintTable::select_depth(); nullptr: every selection takes its two passes
+    unsigned int tiles_x, tile_rows;    // the tile grid: a tile's selection also looks at its neighbours' hints
+    unsigned int grid;              // workgroups (each strides over the tile order); 0 = an eighth of the tiles
+    bool at_rest;                   // the camera of the last frames: selections sized tightly
+    int hint_radius;                // a tile's selection is sized from its own walks' need and its neighbours' within this many tiles
+};
+void launch_select(const SelectArgs& a);
+
+struct CompositeArgs {
+    hipStream_t s; const LaunchKnobs* knobs; unsigned int n_tiles; FrameConst fc;
+    TileLists lists;                // near_m != nullptr (with keys2): near selection -- launch_select ran in front: of a list of more than
+                                    // 2048 keys only the nearest near_m[tile] are in order (composite_tile)
+    KeyBuffers keys;                // keys2 != nullptr: no sort launch ran; lists of more than 2048 keys are sorted by their tile's
+                                    // workgroup through this buffer
+    const Rec* recs; uint32_t* argb; FrameStatus* status; const unsigned int* orig;
+    unsigned int fused_sort_max;    // see SortArgs
+    uint2* iters;                   // per wave (scan, blend) iteration counts, statistics frames only
+    bool keep_keys;                 // lists sorted inside the compositor are also written back to the bucket (the debug getters
+                                    // read them there); off on ordinary frames
+    bool pair_walk;                 // the two-records-per-step flavour of the exact walk (same pixels)
+    bool libm_exp;                  // SPLAT_MODE_LIBM_EXP: expf as the host libm computes it
+    bool clear_first;               // the frame starts from a cleared image: old pixels are not read, tiles nothing covers are zeroed
+                                    // (color.clear(0) of src/main.rs:73, fused)
+    HintTable hints;                // needs(): how many of its list's nearest keys each wave's walk needed (sizes the next frame's selection);
+                                    // starts(): where each wave's exact walk started, in keys from the list's near end (fc.start_hints);
+                                    // refinement(): each wave's start refinement at rest (composite_tile, phase A)
+    unsigned int refine;            // != 0: this frame's waves refine their starts (splat_policy_decision::refine)
+};
+void launch_composite(const CompositeArgs& a);
 hipError_t init_device_kernels();   // per-device kernel attributes; call with the device current
 
 // ---- splat_multi.hip: the multi-GPU layer's hooks into a context (splat_ctx itself stays private to splat_api.hip)

@@ -3506,12 +3506,6 @@ __global__ __launch_bounds__(256, (LONGM != 0 && !PAIR) ? 7 : SPLAT_COMP_WAVES) 
 // ---------------------------------------------------------------------------
 // launch wrappers
 // ---------------------------------------------------------------------------
-// Experiment switches of the launches below: the CONTEXT's (read from the environment at splat_create), handed over by
-// the API layer for the calling thread before it enqueues a frame -- two contexts of one process may differ.
-static const LaunchKnobs g_default_knobs{};
-static thread_local const LaunchKnobs* g_knobs = &g_default_knobs;
-void use_launch_knobs(const LaunchKnobs* k) { g_knobs = k ? k : &g_default_knobs; }
-static unsigned int sort_radix_min() { return g_knobs->sort_radix_min; }
 static inline unsigned int blocks_for(uint64_t n, unsigned int bs) { return (unsigned int)((n + bs - 1) / bs); }
 
 // Per-DEVICE kernel attributes (the large sort classes need more dynamic LDS than the default limit): called by
@@ -3568,43 +3562,48 @@ void launch_block_bounds(hipStream_t s, uint64_t n, const float* pos4, const flo
     if (!n) return;
     hipLaunchKernelGGL(block_bounds_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, n, pos4, cov3d, orig, bounds);
 }
-void launch_preprocess(hipStream_t s, uint64_t n, const float4* planes, const unsigned int* orig, FrameConst fc, Rec* recs,
-                       float* depth, ushort4* rect, unsigned int* counts, unsigned int* vislist, unsigned long long* keys,
-                       const BlockBounds* bounds, unsigned int* blockinfo, FrameStatus* status, const unsigned int* layout, bool count_only,
-                       uint4* large_list, unsigned int* large_count) {
+void launch_preprocess(const BinArgs& a) {
+    const uint64_t n = a.scene.n;
     if (!n) return;
+    const BlockBounds* bounds = a.scene.bounds;
+    unsigned int *counts = a.bin.cursors, *blockinfo = a.blockinfo, *large_count = a.large.count;
+    const unsigned int* layout = a.bin.layout;
+    uint4* large_list = a.large.list;
+    FrameConst fc = a.fc;
     if (!bounds || !blockinfo) fc.cull_blocks = 0;
     if (!blockinfo || !layout) fc.bucket_cap = 0;
     if (!large_count || !fc.bucket_cap) { large_list = nullptr; large_count = nullptr; }      // (a counter without a list: large splats are only counted)
     const dim3 grid(blocks_for(n, 256)), block(256);
-    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, block, g_knobs->k1_lds_pad, s, n, planes, orig, fc, recs, depth, rect, counts, vislist, keys, bounds, blockinfo, status, large_list, large_count); };
-    if (fc.bucket_cap && count_only) { if (fc.corrected) go(preprocess_kernel<true, true, true>); else go(preprocess_kernel<true, false, true>); }
+    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, block, a.knobs->k1_lds_pad, a.s, n, a.scene.planes, a.scene.orig, fc, a.recs, a.depth, a.rect, counts, a.vislist, a.keys, bounds, blockinfo, a.status, large_list, large_count); };
+    if (fc.bucket_cap && a.count_only) { if (fc.corrected) go(preprocess_kernel<true, true, true>); else go(preprocess_kernel<true, false, true>); }
     else if (fc.bucket_cap && fc.corrected) go(preprocess_kernel<true, true>);
     else if (fc.bucket_cap) go(preprocess_kernel<true, false>);
     else if (fc.corrected) go(preprocess_kernel<false, true>);
     else go(preprocess_kernel<false, false>);
 }
-void launch_bin_large(hipStream_t s, const FrameConst& fc, const uint4* large_list, const unsigned int* large_count, unsigned int large_cap, unsigned int* cursors,
-                      unsigned long long* keys, const FrameStatus* status, bool count_only) {
+void launch_bin_large(const BinArgs& a) {
+    const FrameConst& fc = a.fc;
+    const uint4* large_list = a.large.list;
+    const unsigned int* large_count = a.large.count;
     if (!large_list || !large_count || !fc.bucket_cap || fc.tiles_x <= 0 || fc.n_tile_rows <= 0) return;
     const unsigned int groups = (unsigned int)((fc.tiles_x + LARGE_G - 1) / LARGE_G) * (unsigned int)((fc.n_tile_rows + LARGE_G - 1) / LARGE_G);
-    if (count_only)
-        hipLaunchKernelGGL(bin_large_kernel<true>, dim3(groups), dim3(256), 0, s, large_list, large_count, large_cap, cursors, keys, fc.bucket_cap, fc.tiles_x, fc.n_tile_rows,
-                           status, fc.redo_only ? 1u : 0u);
-    else
-        hipLaunchKernelGGL(bin_large_kernel<false>, dim3(groups), dim3(256), 0, s, large_list, large_count, large_cap, cursors, keys, fc.bucket_cap, fc.tiles_x, fc.n_tile_rows,
-                           status, fc.redo_only ? 1u : 0u);
+    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(groups), dim3(256), 0, a.s, large_list, large_count, a.large.cap, a.bin.cursors, a.keys, fc.bucket_cap, fc.tiles_x, fc.n_tile_rows,
+                                                  a.status, fc.redo_only ? 1u : 0u); };
+    if (a.count_only) go(bin_large_kernel<true>); else go(bin_large_kernel<false>);
 }
-void launch_scan(hipStream_t s, unsigned int m, unsigned int* counts, unsigned int* offsets, unsigned int* cursor,
-                 unsigned int* order, unsigned int* lens, FrameStatus* status, unsigned long long capacity,
-                 unsigned int bucket_cap, unsigned int grid_big, unsigned int grid_mid, unsigned int grid_long,
-                 FrameStatus* host_status, const unsigned int* layout, unsigned int* next_layout, unsigned int* next_counts, float spare_max,
-                 bool redo_only, unsigned int* off2, unsigned int cap2, unsigned int* large_count, unsigned int tiles_x, unsigned int motion_radius) {
+void launch_scan(const ScanArgs& a) {
+    hipStream_t s = a.s;
+    const unsigned int m = a.m, bucket_cap = a.bucket_cap, grid_big = a.grids.big, grid_mid = a.grids.mid, grid_long = a.grids.lng;
+    unsigned int *counts = a.bin.cursors, *offsets = a.lists.offsets, *order = a.lists.order, *lens = a.lists.lens;
+    const unsigned int* layout = a.bin.layout;
     if (bucket_cap && layout)
     {
+        unsigned int *next_layout = a.next.to.layout, *next_counts = a.next.to.cursors;
+        const unsigned int tiles_x = a.next.tiles_x, cap2 = a.keys.cap2;
+        unsigned int motion_radius = a.next.motion_radius;
         const unsigned int nwg = (next_layout && next_counts) ? 2u : 1u;
         // small grids: 256 threads start at once beside a busy compositor; 4K-sized ones need the width
-        const int nt = g_knobs->scan_threads ? g_knobs->scan_threads : (m > 12000u ? 1024 : 256);
+        const int nt = a.knobs->scan_threads ? a.knobs->scan_threads : (m > 12000u ? 1024 : 256);
         // one byte of LDS per tile for the length classes (up to 48 KB: a 6-megapixel target), else they are re-read
         const unsigned int cls_bytes = (m + 15u) & ~15u, in_lds = cls_bytes <= 49152u ? 1u : 0u;
         // (the layout workgroup's motion filter: two u16 per tile -- up to 12 288 tiles, a 1440p target; larger ones keep the
@@ -3613,45 +3612,49 @@ void launch_scan(hipStream_t s, unsigned int m, unsigned int* counts, unsigned i
         if (nwg < 2u || mv_bytes > 49152u || tiles_x == 0u) motion_radius = 0u;
         motion_radius = std::min(motion_radius, 12u);          // (build_layout's window: RMAX)
         const unsigned int dyn = std::max(in_lds ? cls_bytes : 0u, motion_radius ? mv_bytes : 0u);
-        if (nt == 256)
-            hipLaunchKernelGGL(scan_bucket_kernel<256>, dim3(nwg), dim3(256), dyn, s, m, counts, offsets, order, lens, status, layout,
-                               grid_big, grid_mid, grid_long, in_lds, host_status, next_layout, next_counts, bucket_cap, spare_max, redo_only ? 1u : 0u, off2, cap2, large_count, tiles_x, motion_radius);
-        else if (nt == 512)
-            hipLaunchKernelGGL(scan_bucket_kernel<512>, dim3(nwg), dim3(512), dyn, s, m, counts, offsets, order, lens, status, layout,
-                               grid_big, grid_mid, grid_long, in_lds, host_status, next_layout, next_counts, bucket_cap, spare_max, redo_only ? 1u : 0u, off2, cap2, large_count, tiles_x, motion_radius);
-        else
-            hipLaunchKernelGGL(scan_bucket_kernel<1024>, dim3(nwg), dim3(1024), dyn, s, m, counts, offsets, order, lens, status, layout,
-                               grid_big, grid_mid, grid_long, in_lds, host_status, next_layout, next_counts, bucket_cap, spare_max, redo_only ? 1u : 0u, off2, cap2, large_count, tiles_x, motion_radius);
+        auto go = [&](auto kern, unsigned int threads) {
+            hipLaunchKernelGGL(kern, dim3(nwg), dim3(threads), dyn, s, m, counts, offsets, order, lens, a.status, layout, grid_big, grid_mid, grid_long, in_lds, a.host_status,
+                               next_layout, next_counts, bucket_cap, a.spare_max, a.redo_only ? 1u : 0u, a.lists.off2, cap2, a.large_count, tiles_x, motion_radius);
+        };
+        if (nt == 256) go(scan_bucket_kernel<256>, 256u);
+        else if (nt == 512) go(scan_bucket_kernel<512>, 512u);
+        else go(scan_bucket_kernel<1024>, 1024u);
     }
     else
-        hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, s, m, counts, offsets, cursor, order, lens, status, capacity,
-                           bucket_cap, grid_big, grid_mid, grid_long, host_status);
+        hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, s, m, counts, offsets, a.lists.cursor, order, lens, a.status, a.keys.cap,
+                           bucket_cap, grid_big, grid_mid, grid_long, a.host_status);
 }
-void launch_layout(hipStream_t s, unsigned int m, const unsigned int* counts, const unsigned int* layout, unsigned int* next_layout,
-                   unsigned int* next_counts, unsigned int key_entries, FrameStatus* status, FrameStatus* host_status, float spare_max,
-                   const FrameStatus* redo_gate, unsigned int* large_count) {
+void launch_layout(const LayoutArgs& a) {
+    hipStream_t s = a.s;
+    const unsigned int m = a.m;
+    const unsigned int *counts = a.from.cursors, *layout = a.from.layout;
+    unsigned int *next_layout = a.next.layout, *next_counts = a.next.cursors;
+    const FrameStatus* redo_gate = a.redo_gate;
     if (redo_gate != nullptr && m <= 12000u)        // (above that -- a 4K target -- the launch keeps its sixteen waves, as the scan does: when it does run, it runs long)
-        hipLaunchKernelGGL(layout_kernel<256>, dim3(1), dim3(256), 0, s, m, counts, layout, next_layout, next_counts, key_entries, status, host_status, spare_max, redo_gate, large_count);
+        hipLaunchKernelGGL(layout_kernel<256>, dim3(1), dim3(256), 0, s, m, counts, layout, next_layout, next_counts, a.key_entries, a.status, a.host_status, a.spare_max, redo_gate, a.large_count);
     else
-        hipLaunchKernelGGL(layout_kernel<1024>, dim3(1), dim3(1024), 0, s, m, counts, layout, next_layout, next_counts, key_entries, status, host_status, spare_max, redo_gate, large_count);
+        hipLaunchKernelGGL(layout_kernel<1024>, dim3(1), dim3(1024), 0, s, m, counts, layout, next_layout, next_counts, a.key_entries, a.status, a.host_status, a.spare_max, redo_gate, a.large_count);
 }
-void launch_emit(hipStream_t s, uint64_t n, FrameConst fc, const float* depth, const ushort4* rect, const unsigned int* orig,
-                 const unsigned int* vislist, unsigned int* cursor, unsigned long long* keys, const FrameStatus* status) {
-    if (!n) return;
-    hipLaunchKernelGGL(emit_kernel, dim3(blocks_for(n, 256 * EMIT_G)), dim3(256), 0, s, fc, depth, rect, orig, vislist, cursor, keys, status);
+void launch_emit(const EmitArgs& a) {
+    if (!a.scene.n) return;
+    hipLaunchKernelGGL(emit_kernel, dim3(blocks_for(a.scene.n, 256 * EMIT_G)), dim3(256), 0, a.s, a.fc, a.depth, a.rect, a.scene.orig, a.vislist, a.cursor, a.keys, a.status);
 }
-void launch_sort(hipStream_t s, unsigned int n_tiles, unsigned int grid_big, unsigned int grid_mid, unsigned int grid_long, const unsigned int* offsets,
-                 const unsigned int* order, const unsigned int* lens, unsigned long long* keys, unsigned long long* keys2,
-                 FrameStatus* status, const unsigned int* orig, unsigned int fused_sort_max, const unsigned int* off2) {
+void launch_sort(const SortArgs& a) {
+    hipStream_t s = a.s;
+    const unsigned int n_tiles = a.n_tiles, fused_sort_max = a.fused_sort_max;
     if (!n_tiles) return;
+    const unsigned int *offsets = a.lists.offsets, *order = a.lists.order, *lens = a.lists.lens, *orig = a.orig;
+    const unsigned int* off2 = a.lists.off2;
     if (!off2) off2 = offsets;          // (two-pass binning: the second buffer mirrors the first, list for list)
-    const unsigned int radix_min = sort_radix_min();
+    unsigned long long *keys = a.keys.keys, *keys2 = a.keys.keys2;
+    FrameStatus* status = a.status;
+    const unsigned int radix_min = a.knobs->sort_radix_min;
     // longest class first (the tiles are ordered longest-first too)
-    grid_big = std::min(grid_big, n_tiles); grid_mid = std::min(grid_mid, n_tiles);
+    const unsigned int grid_big = std::min(a.grids.big, n_tiles), grid_mid = std::min(a.grids.mid, n_tiles);
     if (grid_big) {
         // four workgroups per list: lists of 16385..65536 keys are sorted as runs of 16384 and merged
         // (two-pass binning only: one-pass buckets hold at most 16384 keys and there is no keys2)
-        grid_long = keys2 ? std::min(grid_long, grid_big) : 0u;
+        const unsigned int grid_long = keys2 ? std::min(a.grids.lng, grid_big) : 0u;
         hipLaunchKernelGGL((sort_tiles_kernel<1024, 16384>), dim3(grid_big + 3u * grid_long), dim3(1024), (sort_lds_bytes<1024, 16384>()), s,
                            offsets, order, lens, keys, keys2, status, 8192u, radix_min, keys2 ? 4 : 1, grid_big, std::max(grid_long, 1u), orig, off2);
         if (grid_long)
@@ -3665,49 +3668,50 @@ void launch_sort(hipStream_t s, unsigned int n_tiles, unsigned int grid_big, uns
         hipLaunchKernelGGL((sort_tiles_kernel<256, 2048>), dim3(n_tiles), dim3(256), (sort_lds_bytes<256, 2048>()), s, offsets, order,
                            lens, keys, keys2, status, fused_sort_max, radix_min, 0, 0u, 1u, orig, off2);
 }
-void launch_select(hipStream_t s, unsigned int n_tiles, const unsigned int* offsets, const unsigned int* order, const unsigned int* lens,
-                   unsigned long long* keys, unsigned long long* keys2, FrameStatus* status, const unsigned int* orig, unsigned int near_cap,
-                   const unsigned int* need_hint, unsigned int* near_m, unsigned int tiles_x, unsigned int tile_rows, unsigned int* near_thr, unsigned int grid, bool at_rest,
-                   const unsigned int* off2, int hint_radius) {
+void launch_select(const SelectArgs& a) {
+    const unsigned int n_tiles = a.n_tiles;
     if (!n_tiles) return;
-    if (!off2) off2 = offsets;
-    if (g_knobs->dbg_hint_radius >= 0) hint_radius = g_knobs->dbg_hint_radius;
-    if (g_knobs->dbg_select_stride) grid = (n_tiles + g_knobs->dbg_select_stride - 1u) / g_knobs->dbg_select_stride;
+    const unsigned int* off2 = a.lists.off2;
+    if (!off2) off2 = a.lists.offsets;
+    int hint_radius = a.hint_radius;
+    unsigned int grid = a.grid;
+    if (a.knobs->dbg_hint_radius >= 0) hint_radius = a.knobs->dbg_hint_radius;
+    if (a.knobs->dbg_select_stride) grid = (n_tiles + a.knobs->dbg_select_stride - 1u) / a.knobs->dbg_select_stride;
     if (!grid) grid = (n_tiles + 7u) / 8u;
-    hipLaunchKernelGGL(select_near_kernel, dim3(std::min(grid, n_tiles)), dim3(256), 0, s, offsets, order, lens, keys, keys2, status, orig, sort_radix_min(),
-                       std::min(std::max(near_cap, 64u), 2048u), need_hint, near_m, tiles_x, tile_rows, near_thr, n_tiles, at_rest ? 1u : 0u, off2, std::min(std::max(hint_radius, 0), 7));
+    hipLaunchKernelGGL(select_near_kernel, dim3(std::min(grid, n_tiles)), dim3(256), 0, a.s, a.lists.offsets, a.lists.order, a.lists.lens, a.keys.keys, a.keys.keys2, a.status, a.orig, a.knobs->sort_radix_min,
+                       std::min(std::max(a.near_cap, 64u), 2048u), a.need_hint, a.lists.near_m, a.tiles_x, a.tile_rows, a.near_thr, n_tiles, a.at_rest ? 1u : 0u, off2, std::min(std::max(hint_radius, 0), 7));
 }
-void launch_composite(hipStream_t s, unsigned int n_tiles, FrameConst fc, const unsigned int* offsets,
-                      const unsigned int* order, const unsigned int* lens, unsigned long long* keys, const Rec* recs,
-                      uint32_t* argb, FrameStatus* status, const unsigned int* orig, unsigned int fused_sort_max, uint2* iters,
-                      bool keep_keys, bool pair_walk, bool libm_exp, bool clear_first, unsigned long long* keys2, const unsigned int* near_m,
-                      unsigned int* need_hint, unsigned int* start_hint, const unsigned int* off2, unsigned int* probe_hint,
-                      unsigned int refine) {
+void launch_composite(const CompositeArgs& c) {
+    unsigned int n_tiles = c.n_tiles;
     if (!n_tiles) return;
-    if (!off2) off2 = offsets;
-    if (g_knobs->dbg_ntiles) n_tiles = std::min(n_tiles, g_knobs->dbg_ntiles);   // debug: composite only the N longest tiles
+    const unsigned int* off2 = c.lists.off2;
+    if (!off2) off2 = c.lists.offsets;
+    if (c.knobs->dbg_ntiles) n_tiles = std::min(n_tiles, c.knobs->dbg_ntiles);   // debug: composite only the N longest tiles
     // SPLAT_COMP_LDS_PAD: extra dynamic LDS per workgroup, i.e. an occupancy cap (12 KB are in use:
     // 13 workgroups fit a CU's LDS, 8 its wave slots) -- for overlapping the next frame's K1
-    const unsigned int pad = g_knobs->comp_lds_pad;
+    const unsigned int pad = c.knobs->comp_lds_pad;
+    unsigned long long* keys2 = c.keys.keys2;
+    const unsigned int* near_m = c.lists.near_m;
+    unsigned int *need_hint = c.hints.needs(), *start_hint = c.hints.starts(), *probe_hint = c.hints.refinement();
     const bool near = near_m != nullptr && keys2 != nullptr && need_hint != nullptr;
-    const unsigned int flags = (keep_keys ? 1u : 0u) | (g_knobs->dbg_starts ? 2u : 0u);
+    const unsigned int flags = (c.keep_keys ? 1u : 0u) | (c.knobs->dbg_starts ? 2u : 0u);
     CompArgs a;
-    a.fc = fc; a.offsets = offsets; a.order = order; a.lens = lens; a.keys = keys; a.recs = recs; a.argb = argb; a.status = status;
-    a.fused_sort_max = fused_sort_max; a.radix_min = sort_radix_min(); a.iters = iters; a.keep_keys = flags; a.clear_first = clear_first ? 1u : 0u;
-    a.orig = orig; a.keys2 = keys2; a.near_m = near_m; a.need_hint = near ? need_hint : nullptr; a.start_hint = start_hint; a.off2 = off2;
-    a.probe_hint = probe_hint; a.refine = (probe_hint != nullptr && start_hint != nullptr) ? refine : 0u;
-    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(n_tiles), dim3(256), pad, s, a); };
+    a.fc = c.fc; a.offsets = c.lists.offsets; a.order = c.lists.order; a.lens = c.lists.lens; a.keys = c.keys.keys; a.recs = c.recs; a.argb = c.argb; a.status = c.status;
+    a.fused_sort_max = c.fused_sort_max; a.radix_min = c.knobs->sort_radix_min; a.iters = c.iters; a.keep_keys = flags; a.clear_first = c.clear_first ? 1u : 0u;
+    a.orig = c.orig; a.keys2 = keys2; a.near_m = near_m; a.need_hint = near ? need_hint : nullptr; a.start_hint = start_hint; a.off2 = off2;
+    a.probe_hint = probe_hint; a.refine = (probe_hint != nullptr && start_hint != nullptr) ? c.refine : 0u;
+    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(n_tiles), dim3(256), pad, c.s, a); };
     if (near) {         // (a tile the selection does not serve repairs itself: no launch behind this one)
-        if (libm_exp) go(composite_exact_kernel<false, true, 2>);
-        else if (pair_walk) go(composite_exact_kernel<true, false, 2>);
+        if (c.libm_exp) go(composite_exact_kernel<false, true, 2>);
+        else if (c.pair_walk) go(composite_exact_kernel<true, false, 2>);
         else go(composite_exact_kernel<false, false, 2>);
     } else if (keys2 != nullptr) {
-        if (libm_exp) go(composite_exact_kernel<false, true, 1>);
-        else if (pair_walk) go(composite_exact_kernel<true, false, 1>);
+        if (c.libm_exp) go(composite_exact_kernel<false, true, 1>);
+        else if (c.pair_walk) go(composite_exact_kernel<true, false, 1>);
         else go(composite_exact_kernel<false, false, 1>);
     } else {
-        if (libm_exp) go(composite_exact_kernel<false, true, 0>);
-        else if (pair_walk) go(composite_exact_kernel<true, false, 0>);
+        if (c.libm_exp) go(composite_exact_kernel<false, true, 0>);
+        else if (c.pair_walk) go(composite_exact_kernel<true, false, 0>);
         else go(composite_exact_kernel<false, false, 0>);
     }
 }
