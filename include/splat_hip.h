@@ -37,6 +37,9 @@ extern "C" {
  * passes the shorter struct has 16 bytes written past it) compares the two before its first call -- the ctypes binding,
  * rust/src/pipelines_hip.rs and the C++ host mirror all do -- and splat_stats_size() tells the byte count it will write. */
 #define SPLAT_ABI_VERSION 7
+/* Added under version 7, with no change to any struct or earlier entry point: splat_decode_ply_device and
+ * splat_upload_ply_device (and the splat_ply_layout they take).  A library of version 7 may predate them: a binding
+ * that wants them finds them by symbol (dlsym / hasattr) and does without them where they are missing. */
 
 /* modes: bit flags, 0 = the default */
 #define SPLAT_MODE_EXACT 0       /* back-to-front, 8-bit truncation per splat as blend() does it; the exponential of
@@ -141,6 +144,38 @@ int splat_upload_scene_device(splat_ctx* ctx, uint64_t n, const void* d_pos4, co
 /* compute_cov3d with device in, device out (no copies); producer_stream as above.  Returns when d_cov3d_out is written. */
 int splat_compute_cov3d_device(splat_ctx* ctx, uint64_t n, const void* d_scales3, const void* d_rot4,
                                void* d_cov3d_out, void* producer_stream);
+/* The scene from PLY vertex rows in DEVICE memory (the INRIA layout of SURVEY.md appendix C, or any other property
+ * list): what load_from_ply does between the file and the upload (src/gaussians.rs:246-283, 375-405) -- exp of the
+ * scales, the sigmoid of the opacity, the quaternion reordered, the mean position subtracted, that mean from ONE
+ * sequential f32 sum in index order -- on the GPU, with the host loader's results bit for bit.
+ * splat_ply_layout says where in a row the float32 property feeding each destination slot lies.  Slots: */
+#define SPLAT_PLY_SLOT_POS 0      /* 0-2   x y z                                   -> pos4 (w = 1)            */
+#define SPLAT_PLY_SLOT_SCALE 3    /* 3-5   scale_0..2, expf                        -> scales3                 */
+#define SPLAT_PLY_SLOT_OPACITY 6  /* 6     opacity, 1 / (1 + expf(-v))             -> opacity                 */
+#define SPLAT_PLY_SLOT_ROT 7      /* 7-10  rot_1 rot_2 rot_3 rot_0                 -> rot4 (i, j, k, w)       */
+#define SPLAT_PLY_SLOT_SH 11      /* 11-13 f_dc_0..2, 14-58 f_rest_0..44           -> sh[0..48), no transpose */
+#define SPLAT_PLY_SLOTS 59
+typedef struct {
+    uint64_t n;                       /* vertices */
+    uint32_t stride;                  /* bytes per vertex row, >= 1 */
+    int32_t  offset[SPLAT_PLY_SLOTS]; /* byte offset in a row of the float32 property feeding slot k, -1 = absent */
+} splat_ply_layout;
+/* An absent property keeps Gaussian::new's value: 0 (a scale of 0, not exp(0); an opacity of 0), the quaternion
+ * (0, 0, 0, 1).  Nothing is assumed about alignment: d_rows may be any byte address, the stride any number >= 1 (files
+ * with uchar properties have strides like 251); little-endian floats are put together from the bytes they occupy.
+ * SPLAT_ERR_INVALID, before any device work: a NULL context, layout or (with n > 0) pointer, stride == 0, an offset
+ * below -1, offset + 4 > stride.
+ * splat_decode_ply_device: into the caller's five device buffers (pos4 4n, scales3 3n, opacity n, rot4 4n, sh 48n
+ * floats, 4-byte aligned), all required.  producer_stream as for splat_upload_scene_device; synchronous. */
+int splat_decode_ply_device(splat_ctx* ctx, const splat_ply_layout* layout, const void* d_rows, void* d_pos4,
+                            void* d_scales3, void* d_opacity, void* d_rot4, void* d_sh, void* producer_stream);
+/* splat_upload_ply_device: the same chain into temporaries of the library, then cov3d -- compute_cov3d (kernel K0) when
+ * compute_cov3d != 0, which is GaussianList::from_vec and the loop of src/main.rs:24-26; all zero otherwise, which is
+ * Gaussian::new -- then splat_upload_scene_device.  Nothing returns to the host.  Synchronous: on return d_rows may be
+ * freed and the temporaries are gone.  n == 0: as splat_upload_scene_device with n == 0. */
+int splat_upload_ply_device(splat_ctx* ctx, const splat_ply_layout* layout, const void* d_rows, int32_t compute_cov3d,
+                            void* producer_stream);
+
 /* Debug / stage parity: the stored scene order and K1 block bounds of the current scene.
  * orig_out: n u32 (slot j holds original Gaussian orig[j]); bounds_out: ceil(n/256) x 8 f32
  * (lo[3], hi[3], fmax, pad), either may be NULL.  n and n_blocks must be the scene's. */

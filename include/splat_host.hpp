@@ -69,6 +69,20 @@ struct GaussianList;
 // the SoA upload buffers, on `threads` host threads (0 = all).  cov3d is left zero (compute_cov3d, K0 on the GPU).
 GaussianList load_from_ply_soa(const std::string& filename, int threads = 0);
 long long ply_vertex_count(const std::string& filename);      // header only
+// Where the loader finds its properties: the splat_ply_layout the device decoder takes (a known name whose type is not
+// float is absent; of duplicated names the last wins -- as load_from_ply reads them) and where the vertex rows lie in
+// the file.  binary == false (an ascii file): the rows are text and the offsets describe nothing.
+struct PlyLayout {
+    splat_ply_layout layout;
+    bool binary = false;
+    uint64_t payload_offset = 0, payload_bytes = 0;
+};
+PlyLayout ply_layout(const std::string& filename);
+// load_from_ply + compute_cov3d + upload as one call whose work is the GPU's: the payload of a binary file is copied to
+// the device once, as it is, and decoded, activated, recentred and uploaded there (splat_upload_ply_device); an ascii
+// file goes through the host loader and splat_upload_scene.  compute_cov3d == false leaves cov3d zero (Gaussian::new).
+// Returns the number of Gaussians; the frames are those of the host path, byte for byte.
+uint64_t load_ply_to_gpu(splat_ctx* ctx, const std::string& filename, bool compute_cov3d = true);
 
 struct GaussianList {           // src/gaussians.rs:408-416, SoA
     std::vector<float> positions;   // 4 x N (x,y,z,1)
@@ -115,6 +129,7 @@ protected:
     void render_frame(const GaussianList& g, const Camera& cam, float lowpass, uint32_t* color);
     void stream(const GaussianList& g, const Camera& cam, float lowpass, uint32_t* color);
     void ensure(const GaussianList& g);
+    void create_context();
     splat_ctx* ctx_ = nullptr;
     const void* uploaded_ = nullptr;
     int mode_ = 0;
@@ -128,6 +143,9 @@ public:
     void render_to_buffer(uint32_t* color);
     void render_frame_to_buffer(uint32_t* color);   // clear + render_to_buffer, src/main.rs:73-74, in one call (see PipelineBase)
     void stream_frame(uint32_t* color);        // cleared frame, asynchronous (see PipelineBase)
+    // The scene straight from a PLY file through load_ply_to_gpu: `gaussians` is left empty, the context holds the scene
+    // (invalidate_scene() or a change of `gaussians` goes back to the host copy).  Returns the number of Gaussians.
+    uint64_t load_ply_gpu(const std::string& filename, bool compute_cov3d = true);
     std::vector<Gaussian> gaussians;   // pub
     Camera camera;                     // pub
 private:

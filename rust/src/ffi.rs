@@ -69,6 +69,14 @@ pub struct SplatStats {
     pub n_near_tiles: u64, pub n_near_fallback: u64,
 }
 
+pub const SPLAT_PLY_SLOTS: usize = 59;
+// where in a vertex row the float32 property feeding each destination slot lies (-1 = absent); slots: 0-2 x y z,
+// 3-5 scale_0..2, 6 opacity, 7-10 rot_1 rot_2 rot_3 rot_0, 11-13 f_dc_0..2, 14-58 f_rest_0..44
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct SplatPlyLayout {
+    pub n: u64, pub stride: u32, pub offset: [i32; SPLAT_PLY_SLOTS],
+}
+
 #[repr(C)] #[derive(Clone, Copy, Default)]
 pub struct SplatRecord {
     pub cx: f32, pub cy: f32, pub hx: f32, pub hy: f32,
@@ -93,6 +101,13 @@ extern "C" {
                                      d_opacity: *const c_void, d_sh: *const c_void, producer_stream: *mut c_void) -> c_int;
     pub fn splat_compute_cov3d_device(ctx: *mut SplatCtx, n: u64, d_scales3: *const c_void, d_rot4: *const c_void,
                                       d_cov3d_out: *mut c_void, producer_stream: *mut c_void) -> c_int;
+    // the scene from PLY vertex rows in DEVICE memory: decoded, activated and recentred as load_from_ply does, on the GPU
+    // (added under ABI version 7: a library of that version may predate them -- look them up by symbol where that matters)
+    pub fn splat_decode_ply_device(ctx: *mut SplatCtx, layout: *const SplatPlyLayout, d_rows: *const c_void, d_pos4: *mut c_void,
+                                   d_scales3: *mut c_void, d_opacity: *mut c_void, d_rot4: *mut c_void, d_sh: *mut c_void,
+                                   producer_stream: *mut c_void) -> c_int;
+    pub fn splat_upload_ply_device(ctx: *mut SplatCtx, layout: *const SplatPlyLayout, d_rows: *const c_void, compute_cov3d: i32,
+                                   producer_stream: *mut c_void) -> c_int;
     // debug / stage parity: the stored order (n u32) and the K1 block bounds (ceil(n/256) x 8 f32); either may be null
     pub fn splat_get_scene_layout(ctx: *mut SplatCtx, orig_out: *mut u32, n: u64, bounds_out: *mut f32, n_blocks: u64) -> c_int;
     pub fn splat_set_slab(ctx: *mut SplatCtx, tile_row0: i32, tile_row1: i32) -> c_int;

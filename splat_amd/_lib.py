@@ -41,6 +41,19 @@ class Record(C.Structure):
                 ("px0", C.c_int32), ("px1", C.c_int32), ("py0", C.c_int32), ("py1", C.c_int32)]
 
 
+PLY_SLOTS = 59
+# destination slots of splat_ply_layout.offset: (first slot, count) per buffer, and the PLY property that feeds each slot
+PLY_SLOT_POS, PLY_SLOT_SCALE, PLY_SLOT_OPACITY, PLY_SLOT_ROT, PLY_SLOT_SH = 0, 3, 6, 7, 11
+PLY_SLOT_NAMES = (["x", "y", "z", "scale_0", "scale_1", "scale_2", "opacity", "rot_1", "rot_2", "rot_3", "rot_0"] +
+                  ["f_dc_%d" % i for i in range(3)] + ["f_rest_%d" % i for i in range(45)])
+
+
+class PlyLayout(C.Structure):
+    """splat_ply_layout: n vertex rows of `stride` bytes; offset[k] = byte offset in a row of the float32 property that
+    feeds slot k (PLY_SLOT_NAMES[k]), -1 = absent"""
+    _fields_ = [("n", C.c_uint64), ("stride", C.c_uint32), ("offset", C.c_int32 * PLY_SLOTS)]
+
+
 # every symbol include/splat_hip.h declares: (name, restype, argtypes)
 _fp = C.POINTER(C.c_float)
 SYMBOLS = [
@@ -54,6 +67,9 @@ SYMBOLS = [
     ("splat_compute_cov3d", C.c_int, [C.c_void_p, C.c_uint64, _fp, _fp, _fp]),
     ("splat_upload_scene_device", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("splat_compute_cov3d_device", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("splat_decode_ply_device", C.c_int, [C.c_void_p, C.POINTER(PlyLayout), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]),
+    ("splat_upload_ply_device", C.c_int, [C.c_void_p, C.POINTER(PlyLayout), C.c_void_p, C.c_int32, C.c_void_p]),
     ("splat_get_scene_layout", C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint64, _fp, C.c_uint64]),
     ("splat_set_slab", C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     ("splat_tile_row_loads", C.c_int, [C.c_void_p, C.POINTER(CameraC), C.POINTER(C.c_uint64), C.c_int32]),

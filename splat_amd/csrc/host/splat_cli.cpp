@@ -13,7 +13,7 @@
 int main(int argc, char** argv) {
     const char* ply = nullptr; const char* out = nullptr;
     int W = 800, H = 600, frames = 36;
-    bool streaming = false, fast = false, one_call = false;
+    bool streaming = false, fast = false, one_call = false, gpu_load = false;
     int in_flight = 2;
     for (int i = 1; i < argc; ++i) {
         if (!std::strcmp(argv[i], "--ply") && i + 1 < argc) ply = argv[++i];
@@ -23,17 +23,23 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[i], "--stream")) streaming = true;
         else if (!std::strcmp(argv[i], "--in-flight") && i + 1 < argc) in_flight = std::max(1, std::min(4, std::atoi(argv[++i])));
         else if (!std::strcmp(argv[i], "--frame")) one_call = true;   // clear + render_to_buffer as ONE call (render_frame_to_buffer) into a pinned `color`
+        else if (!std::strcmp(argv[i], "--gpu-load")) gpu_load = true;   // the PLY's rows are decoded, activated, recentred and uploaded on the GPU (load_ply_to_gpu)
         else if (!std::strcmp(argv[i], "--fast")) fast = true;      // SPLAT_MODE_FAST: every colour byte within 1 of the exact frame
-        else { std::fprintf(stderr, "usage: splat_cli [--ply file] [--size W H] [--frames N] [--frame | --stream [--in-flight 1..4]] [--fast] [--out frame.ppm]\n"); return 2; }
+        else { std::fprintf(stderr, "usage: splat_cli [--ply file] [--size W H] [--frames N] [--frame | --stream [--in-flight 1..4]] [--fast] [--gpu-load] [--out frame.ppm]\n"); return 2; }
     }
     try {
         std::printf("Loading gaussians from %s\n", ply ? ply : "naive_gaussians()");
-        std::vector<splat::Gaussian> g = ply ? splat::load_from_ply(ply) : splat::naive_gaussians();
-        std::printf("Computing cov3d for each gaussian\n");
-        for (auto& x : g) x.compute_cov3d();
+        gpu_load = gpu_load && ply;
+        std::vector<splat::Gaussian> g;
+        if (!gpu_load) {
+            g = ply ? splat::load_from_ply(ply) : splat::naive_gaussians();
+            std::printf("Computing cov3d for each gaussian\n");
+            for (auto& x : g) x.compute_cov3d();
+        }
         splat::Vec3 pos{0.0f, 0.0f, 5.0f};                    // CAMERA_POSITION, src/main.rs:13
         splat::GaussianSplatPipeline01 pipeline(g, splat::Camera((float)H, (float)W, &pos));
         if (fast) pipeline.set_mode(SPLAT_MODE_FAST);
+        if (gpu_load) std::printf("Decoded and uploaded %llu gaussians on the GPU\n", (unsigned long long)pipeline.load_ply_gpu(ply));
         std::vector<uint32_t> color((size_t)W * H, 0u);
         if (streaming) {
             // the same loop with the present step decoupled: `in_flight` pinned frames rotate (2 = a double-buffered window;

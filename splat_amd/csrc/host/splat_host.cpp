@@ -166,16 +166,19 @@ struct PlyFile {
     std::vector<PlyProp> props;
     ~PlyFile() { if (base) munmap((void*)base, len); }
 };
-// destination codes: 0-2 pos, 3-5 scale(exp), 6 opacity(sigmoid), 7-10 rot (i,j,k,w), 11.. sh[k]
+// destination slots: SPLAT_PLY_SLOT_* of include/splat_hip.h, the numbering the device decoder (splat_ply.hip) shares --
+// 0-2 pos, 3-5 scale(exp), 6 opacity(sigmoid), 7-10 rot (i,j,k,w), 11.. sh[k]
+static_assert(SPLAT_PLY_SLOT_POS == 0 && SPLAT_PLY_SLOT_SCALE == 3 && SPLAT_PLY_SLOT_OPACITY == 6 && SPLAT_PLY_SLOT_ROT == 7 &&
+              SPLAT_PLY_SLOT_SH == 11 && SPLAT_PLY_SLOTS == SPLAT_PLY_SLOT_SH + 48, "the name table below is in slot order");
 int ply_dst_of(const std::string& s) {
     static const char* const names[] = {"x", "y", "z", "scale_0", "scale_1", "scale_2", "opacity",
                                         "rot_1", "rot_2", "rot_3", "rot_0", "f_dc_0", "f_dc_1", "f_dc_2"};
-    for (int k = 0; k < 14; ++k)
+    for (int k = 0; k < SPLAT_PLY_SLOT_SH + 3; ++k)
         if (s == names[k]) return k;
     if (s.rfind("f_rest_", 0) == 0) {
         int idx = std::atoi(s.c_str() + 7);
         if (idx < 0 || idx > 44) throw std::runtime_error("f_rest index out of range");   // sh[3+index] would panic
-        return 14 + idx;
+        return SPLAT_PLY_SLOT_SH + 3 + idx;
     }
     return -1;
 }
@@ -230,11 +233,11 @@ void ply_open(const std::string& filename, PlyFile& f) {
 }
 // one decoded value into the SoA arrays (set_property, :261-279)
 inline void ply_store(GaussianList& l, size_t i, int dst, float v) {
-    if (dst < 3) l.positions[4 * i + dst] = v;
-    else if (dst < 6) l.scales[3 * i + dst - 3] = std::exp(v);                   // :264-266
-    else if (dst == 6) l.opacities[i] = 1.0f / (1.0f + std::exp(-v));            // :267
-    else if (dst < 11) l.rotations[4 * i + dst - 7] = v;                         // :268-271
-    else l.sh[48 * i + dst - 11] = v;                                            // :272-279, no transpose
+    if (dst < SPLAT_PLY_SLOT_SCALE) l.positions[4 * i + dst] = v;
+    else if (dst < SPLAT_PLY_SLOT_OPACITY) l.scales[3 * i + dst - SPLAT_PLY_SLOT_SCALE] = std::exp(v);   // :264-266
+    else if (dst == SPLAT_PLY_SLOT_OPACITY) l.opacities[i] = 1.0f / (1.0f + std::exp(-v));               // :267
+    else if (dst < SPLAT_PLY_SLOT_SH) l.rotations[4 * i + dst - SPLAT_PLY_SLOT_ROT] = v;                 // :268-271
+    else l.sh[48 * i + dst - SPLAT_PLY_SLOT_SH] = v;                                                     // :272-279, no transpose
 }
 }  // namespace
 
@@ -292,6 +295,50 @@ GaussianList load_from_ply_soa(const std::string& filename, int threads) {
 
 long long ply_vertex_count(const std::string& filename) { PlyFile f; ply_open(filename, f); return f.n; }
 
+namespace {
+PlyLayout layout_of(const PlyFile& f) {
+    PlyLayout out;
+    out.layout.n = (uint64_t)f.n;
+    out.layout.stride = (uint32_t)f.stride;
+    for (int k = 0; k < SPLAT_PLY_SLOTS; ++k) out.layout.offset[k] = -1;
+    for (const PlyProp& p : f.props)
+        if (p.dst >= 0) out.layout.offset[p.dst] = p.offset;    // of duplicated names the last wins, as in the decode loop
+    out.binary = f.fmt == 1;
+    out.payload_offset = f.payload;
+    out.payload_bytes = out.binary ? (uint64_t)f.n * (uint64_t)f.stride : (uint64_t)(f.len - f.payload);
+    return out;
+}
+}  // namespace
+
+PlyLayout ply_layout(const std::string& filename) { PlyFile f; ply_open(filename, f); return layout_of(f); }
+
+uint64_t load_ply_to_gpu(splat_ctx* ctx, const std::string& filename, bool compute_cov3d) {
+    if (!ctx) throw std::runtime_error("load_ply_to_gpu: no context");
+    PlyFile f;
+    ply_open(filename, f);
+    const PlyLayout pl = layout_of(f);
+    if (!pl.binary) {                                           // text has to be parsed: the host loader, then the host upload
+        GaussianList l = load_from_ply_soa(filename, 0);
+        if (compute_cov3d) l.compute_cov3d(ctx);
+        check(splat_upload_scene(ctx, l.num_gaussians, l.positions.data(), l.cov3d.data(), l.opacities.data(), l.sh.data()),
+              ctx, "splat_upload_scene");
+        return l.num_gaussians;
+    }
+    // binary little endian: the payload crosses PCIe once, as the bytes the file holds
+    void* d_rows = nullptr;
+    if (pl.payload_bytes) {
+        d_rows = splat_device_alloc(ctx, pl.payload_bytes);
+        if (!d_rows) throw std::runtime_error(std::string("splat_device_alloc: ") + splat_last_error(ctx));
+        int rc = splat_device_upload(ctx, d_rows, f.base + pl.payload_offset, pl.payload_bytes);
+        if (rc == SPLAT_OK) rc = splat_upload_ply_device(ctx, &pl.layout, d_rows, compute_cov3d ? 1 : 0, nullptr);
+        splat_device_free(ctx, d_rows);
+        check(rc, ctx, "load_ply_to_gpu");
+    } else {
+        check(splat_upload_ply_device(ctx, &pl.layout, nullptr, compute_cov3d ? 1 : 0, nullptr), ctx, "splat_upload_ply_device");
+    }
+    return pl.layout.n;
+}
+
 // load_from_ply (src/gaussians.rs:375-405): the AoS `Vec<Gaussian>` the reference returns, from the same decode
 std::vector<Gaussian> load_from_ply(const std::string& filename) {
     GaussianList l = load_from_ply_soa(filename, 0);
@@ -346,7 +393,7 @@ void PipelineBase::set_mode(int mode) {
     if (ctx_) throw std::logic_error("set_mode: the GPU context already exists (call before the first frame)");
     mode_ = mode;
 }
-void PipelineBase::ensure(const GaussianList& g) {
+void PipelineBase::create_context() {
     if (!ctx_) {
         // (a libsplat_hip.so built from another header would write a splat_stats of another size into last_stats)
         if (splat_abi_version() != SPLAT_ABI_VERSION || splat_stats_size() != sizeof(splat_stats))
@@ -356,6 +403,9 @@ void PipelineBase::ensure(const GaussianList& g) {
         cfg.mode = mode_;
         if (splat_create(&cfg, &ctx_) != SPLAT_OK) throw std::runtime_error(std::string("splat_create: ") + splat_last_error(nullptr));
     }
+}
+void PipelineBase::ensure(const GaussianList& g) {
+    create_context();
     if (uploaded_ != (const void*)&g) {        // lazily, once per scene object
         check(splat_upload_scene(ctx_, g.num_gaussians, g.positions.data(), g.cov3d.data(), g.opacities.data(), g.sh.data()),
               ctx_, "splat_upload_scene");
@@ -395,6 +445,14 @@ void PipelineBase::free_frame(uint32_t* p) { splat_host_free(p); }
 
 GaussianSplatPipeline01::GaussianSplatPipeline01(std::vector<Gaussian> g, Camera cam)
     : gaussians(std::move(g)), camera(std::move(cam)) {}
+uint64_t GaussianSplatPipeline01::load_ply_gpu(const std::string& filename, bool compute_cov3d) {
+    create_context();
+    gaussians.clear();
+    soa_ = GaussianList();
+    const uint64_t n = load_ply_to_gpu(ctx_, filename, compute_cov3d);
+    uploaded_ = &soa_;                          // the context's scene is the file's; the (empty) host copy is not uploaded over it
+    return n;
+}
 void GaussianSplatPipeline01::render_to_buffer(uint32_t* color) {
     // AoS: cov3d is whatever each Gaussian carries (zero unless the caller ran compute_cov3d, main.rs:24-26)
     if (soa_.num_gaussians != gaussians.size() || uploaded_ == nullptr) soa_ = GaussianList::from_vec(gaussians, false);
@@ -457,6 +515,30 @@ double splat_host_time_load(const char* path, int threads, long long* n_out, cha
     } catch (const std::exception& e) {
         if (err && errlen > 0) { std::strncpy(err, e.what(), errlen - 1); err[errlen - 1] = 0; }
         return -1.0;
+    }
+}
+// ply_layout for ctypes: *binary = 1 for binary little endian (0: ascii -- the offsets then describe nothing)
+int splat_host_ply_layout(const char* path, splat_ply_layout* out, int* binary, unsigned long long* payload_offset,
+                          unsigned long long* payload_bytes, char* err, int errlen) {
+    try {
+        splat::PlyLayout pl = splat::ply_layout(path);
+        if (out) *out = pl.layout;
+        if (binary) *binary = pl.binary ? 1 : 0;
+        if (payload_offset) *payload_offset = pl.payload_offset;
+        if (payload_bytes) *payload_bytes = pl.payload_bytes;
+        return 0;
+    } catch (const std::exception& e) {
+        if (err && errlen > 0) { std::strncpy(err, e.what(), errlen - 1); err[errlen - 1] = 0; }
+        return -1;
+    }
+}
+// load_ply_to_gpu for ctypes: returns n, or -1 with the message in err
+long long splat_host_load_ply_to_gpu(splat_ctx* ctx, const char* path, int compute_cov3d, char* err, int errlen) {
+    try {
+        return (long long)splat::load_ply_to_gpu(ctx, path, compute_cov3d != 0);
+    } catch (const std::exception& e) {
+        if (err && errlen > 0) { std::strncpy(err, e.what(), errlen - 1); err[errlen - 1] = 0; }
+        return -1;
     }
 }
 void splat_host_cov3d(unsigned long long n, const float* scales3, const float* rot4, float* cov3d) {

@@ -92,6 +92,7 @@ struct splat_ctx {
     BlockBounds* bounds = nullptr;         // per K1 block of 256 slots (block culling)
     bool cull_blocks = true;               // SPLAT_CULL=0 disables
     std::vector<unsigned int> h_orig;      // host copy of orig (ensure_h_orig: a device upload leaves it empty until a debug getter asks)
+    float ply_ms[3] = {0.0f, 0.0f, 0.0f};  // device time of decode, sum, subtract inside the most recent PLY decode
     float upload_sort_ms = 0.0f;           // device time of the sort inside the most recent splat_upload_scene_device
     // per-frame buffers
     Slot slots[N_SLOTS];
@@ -1749,6 +1750,107 @@ int splat_upload_scene_device(splat_ctx* c, uint64_t n, const void* d_pos4, cons
 int splat_debug_upload_sort_ms(splat_ctx* c, double* ms) {
     if (!c || !ms) return SPLAT_ERR_INVALID;
     *ms = c->upload_sort_ms;
+    return SPLAT_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// what both PLY entry points refuse before they touch HIP; msg: why
+bool ply_layout_ok(const splat_ply_layout* lay, const char** msg) {
+    if (!lay) { *msg = "NULL layout"; return false; }
+    if (lay->stride == 0) { *msg = "PLY stride is 0"; return false; }
+    for (int k = 0; k < SPLAT_PLY_SLOTS; ++k) {
+        if (lay->offset[k] < -1) { *msg = "PLY property offset below -1"; return false; }
+        if (lay->offset[k] >= 0 && (uint64_t)lay->offset[k] + 4u > lay->stride) { *msg = "PLY property reaches beyond its row"; return false; }
+    }
+    if (lay->n >= 0xFFFFFFFFull) { *msg = "too many Gaussians (index is 32-bit)"; return false; }
+    return true;
+}
+// decode + recentre on the context's stream, behind `producer`, waited for; the mean's three floats are the chain's only
+// temporary.
+hipError_t ply_decode_now(splat_ctx* c, const splat_ply_layout& lay, const void* d_rows, float* pos4, float* scales3,
+                          float* opacity, float* rot4, float* sh, void* producer) {
+    float* d_mean = nullptr;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    auto cleanup = [&] { dfree(d_mean); for (hipEvent_t& x : ev) if (x) { (void)hipEventDestroy(x); x = nullptr; } };
+    hipError_t e;
+#define PLY_TRY(expr) if ((e = (expr)) != hipSuccess) { cleanup(); return e; }
+    PLY_TRY(dmalloc(c, &d_mean, sizeof(float) * 4));
+    for (hipEvent_t& x : ev) PLY_TRY(hipEventCreate(&x));
+    PLY_TRY(follow_producer(c, producer));
+    launch_ply_decode(c->stream, lay, d_rows, pos4, scales3, opacity, rot4, sh, d_mean, ev);
+    PLY_TRY(hipGetLastError());
+    PLY_TRY(hipStreamSynchronize(c->stream));
+#undef PLY_TRY
+    for (int k = 0; k < 3; ++k) { c->ply_ms[k] = 0.0f; (void)hipEventElapsedTime(&c->ply_ms[k], ev[k], ev[k + 1]); }
+    cleanup();
+    return hipSuccess;
+}
+}  // namespace
+
+extern "C" {
+
+int splat_decode_ply_device(splat_ctx* c, const splat_ply_layout* lay, const void* d_rows, void* d_pos4, void* d_scales3,
+                            void* d_opacity, void* d_rot4, void* d_sh, void* producer_stream) {
+    // (the arguments are judged before the context is looked at, and before any HIP call: without a context the reason is
+    // what splat_last_error(NULL) reports)
+    const char* why = nullptr;
+    if (!ply_layout_ok(lay, &why)) return fail(c, SPLAT_ERR_INVALID, why);
+    if (!c) return fail(c, SPLAT_ERR_INVALID, "NULL context");
+    if (lay->n == 0) return SPLAT_OK;
+    if (!d_rows || !d_pos4 || !d_scales3 || !d_opacity || !d_rot4 || !d_sh) return fail(c, SPLAT_ERR_INVALID, "NULL pointer");
+    if (((uintptr_t)d_pos4 & 15u) || (((uintptr_t)d_scales3 | (uintptr_t)d_opacity | (uintptr_t)d_rot4 | (uintptr_t)d_sh) & 3u))
+        return fail(c, SPLAT_ERR_INVALID, "output buffer misaligned (pos4: 16 bytes, the others: 4)");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    hipError_t e = ply_decode_now(c, *lay, d_rows, (float*)d_pos4, (float*)d_scales3, (float*)d_opacity, (float*)d_rot4, (float*)d_sh, producer_stream);
+    if (e != hipSuccess) return fail(c, SPLAT_ERR_HIP, std::string("splat_decode_ply_device: ") + hipGetErrorString(e));
+    return SPLAT_OK;
+}
+
+int splat_upload_ply_device(splat_ctx* c, const splat_ply_layout* lay, const void* d_rows, int32_t compute_cov3d, void* producer_stream) {
+    const char* why = nullptr;
+    if (!ply_layout_ok(lay, &why)) return fail(c, SPLAT_ERR_INVALID, why);
+    if (!c) return fail(c, SPLAT_ERR_INVALID, "NULL context");
+    if (lay->n == 0) return splat_upload_scene_device(c, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
+    if (!d_rows) return fail(c, SPLAT_ERR_INVALID, "NULL pointer");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    const uint64_t n = lay->n;
+    float *d_pos = nullptr, *d_sc = nullptr, *d_op = nullptr, *d_rot = nullptr, *d_sh = nullptr, *d_cov = nullptr;
+    auto cleanup = [&] { dfree(d_pos); dfree(d_sc); dfree(d_op); dfree(d_rot); dfree(d_sh); dfree(d_cov); };
+    hipError_t e;
+#define PLY_TRY(expr)                                                                                      \
+    if ((e = (expr)) != hipSuccess) {                                                                       \
+        cleanup();                                                                                          \
+        return fail(c, SPLAT_ERR_HIP, std::string("splat_upload_ply_device: " #expr ": ") + hipGetErrorString(e)); \
+    }
+    PLY_TRY(dmalloc(c, &d_pos, sizeof(float) * 4 * n));
+    PLY_TRY(dmalloc(c, &d_sc, sizeof(float) * 3 * n));
+    PLY_TRY(dmalloc(c, &d_op, sizeof(float) * n));
+    PLY_TRY(dmalloc(c, &d_rot, sizeof(float) * 4 * n));
+    PLY_TRY(dmalloc(c, &d_sh, sizeof(float) * 48 * n));
+    PLY_TRY(dmalloc(c, &d_cov, sizeof(float) * 9 * n));
+    // cov3d first, on the same stream: K0 behind the decode (GaussianList::from_vec), or zeros (Gaussian::new)
+    PLY_TRY(ply_decode_now(c, *lay, d_rows, d_pos, d_sc, d_op, d_rot, d_sh, producer_stream));
+    if (compute_cov3d) {
+        launch_cov3d(c->stream, n, d_sc, d_rot, d_cov);
+        PLY_TRY(hipGetLastError());
+    } else {
+        PLY_TRY(hipMemsetAsync(d_cov, 0, sizeof(float) * 9 * n, c->stream));
+    }
+    PLY_TRY(hipStreamSynchronize(c->stream));
+#undef PLY_TRY
+    dfree(d_sc); dfree(d_rot);
+    const int rc = splat_upload_scene_device(c, n, d_pos, d_cov, d_op, d_sh, nullptr);
+    cleanup();
+    return rc;
+}
+
+// (debug, not part of the ABI)  Device time of the decode, the sequential sum and the subtraction inside the most recent
+// splat_decode_ply_device / splat_upload_ply_device, in milliseconds.
+int splat_debug_ply_ms(splat_ctx* c, double ms[3]) {
+    if (!c || !ms) return SPLAT_ERR_INVALID;
+    for (int k = 0; k < 3; ++k) ms[k] = c->ply_ms[k];
     return SPLAT_OK;
 }
 

@@ -84,6 +84,44 @@ __host__ __device__ __forceinline__ float exp_libm(float x, const unsigned long 
     return (float)y;
 }
 
+// glibc's expf for EVERY float (the PLY decoder's activations, splat_ply.hip: a log-scale or a logit is whatever the
+// file holds).  The table, the cubic and the FMA-build reduction are exp_libm's, above; what is added is glibc's range
+// handling: NaN stays NaN (x + x), above 0x1.62e42ep6 (log 2^128) the result is +inf, below -0x1.9fe368p6 (log 2^-150)
+// it is +0, and in between nothing is special-cased -- a subnormal result is what the ONE rounding of the double to
+// float gives, which needs float denormals on (the default of a HIP build).  The table is read where it lives: constant
+// memory on the device (a load-time kernel, no LDS copy), the host copy on the host.  Bit-identical to the host libm's
+// expf on every float in [-104, 89] (host compile: tests/test_ply_math_host.py) and on the patterns around every
+// threshold plus a stride sweep of all 2^32 (device compile: tests/test_gpu_ply_device.py).
+__host__ __device__ __forceinline__ float expf_libm_full(float x) {
+    const double InvLn2N = 0x1.71547652b82fep+0 * 32.0, SHIFT = 0x1.8p+52;
+    const double C0 = 0x1.c6af84b912394p-5 / 32.0 / 32.0 / 32.0, C1 = 0x1.ebfce50fac4f3p-3 / 32.0 / 32.0, C2 = 0x1.62e42ff0c52d6p-1 / 32.0;
+#if defined(__HIP_DEVICE_COMPILE__)
+    const unsigned long long* const tab = EXP2F_TAB;
+#else
+    const unsigned long long* const tab = EXP2F_TAB_HOST;
+#endif
+    if (!(fabsf(x) < 88.0f)) {                                 // |x| >= 88, or NaN
+        if (x != x) return x + x;
+        if (x > 0x1.62e42ep6f) return __builtin_huge_valf();   // (+inf among them)
+        if (x < -0x1.9fe368p6f) return 0.0f;                   // (-inf among them)
+    }
+    const double xd = (double)x;
+    const double z = InvLn2N * xd;
+    double kd = z + SHIFT;                                     // round to nearest integer, in the low mantissa bits
+    const unsigned long long ki = __builtin_bit_cast(unsigned long long, kd);
+    kd -= SHIFT;
+    const double r = fma(InvLn2N, xd, -kd);                    // z - kd with the product unrounded: glibc's FMA build (see exp_libm)
+    const double sc = __builtin_bit_cast(double, tab[ki & 31ull] + (ki << 47));
+    const double zz = C0 * r + C1;
+    const double r2 = r * r;
+    double y = C2 * r + 1.0;
+    y = zz * r2 + y;
+    y = y * sc;
+    return (float)y;
+}
+// the loader's sigmoid (src/gaussians.rs:267): IEEE operations around that expf, the divide correctly rounded
+__host__ __device__ __forceinline__ float sigmoid_libm(float v) { return 1.0f / (1.0f + expf_libm_full(-v)); }
+
 // k / 255.0f (IEEE) for every integer k in [0,255] in two instructions: 1/255 split into
 // hi + lo floats, fma(k, hi, k*lo) rounds once (checked exhaustively in tests/test_host.py).
 __host__ __device__ __forceinline__ float div255(float k) {

@@ -153,6 +153,11 @@ void launch_scene_order(hipStream_t s, uint64_t n, const float* pos4, uint32_t* 
 // ... and the bounds of its K1 blocks, as block_bounds of splat_api.hip computes them
 void launch_block_bounds(hipStream_t s, uint64_t n, const float* pos4, const float* cov3d, const unsigned int* orig, BlockBounds* bounds);
 
+// PLY vertex rows -> the five SoA buffers, activated and recentred as load_from_ply does (splat_ply.hip): decode, the
+// sequential sum into mean[3] (device, 3 floats), the subtraction.  ev (nullable): four events recorded around the three.
+void launch_ply_decode(hipStream_t s, const splat_ply_layout& lay, const void* d_rows, float* pos4, float* scales3,
+                       float* opacity, float* rot4, float* sh, float* mean, hipEvent_t* ev = nullptr);
+
 // ---- The per-frame launches take one argument block each, by const&.  The blocks are plain aggregates without defaults: a
 // caller value-initialises one (`ScanArgs a{};`) and what it does not set is zero / nullptr / false.  What travels together
 // is a sub-struct:

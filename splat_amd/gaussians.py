@@ -170,6 +170,42 @@ def load_from_ply(filename):
     return GaussianList(pos4, sc, op, rot, sh)
 
 
+class PlyFileLayout:
+    """What ply_layout() returns: layout (_lib.PlyLayout: n, stride, offset[59]), binary (False: an ascii file, whose
+    offsets describe nothing), payload_offset / payload_bytes (where the vertex rows lie in the file)."""
+
+    def __init__(self, layout, binary, payload_offset, payload_bytes):
+        self.layout, self.binary = layout, bool(binary)
+        self.payload_offset, self.payload_bytes = int(payload_offset), int(payload_bytes)
+        self.n, self.stride = int(layout.n), int(layout.stride)
+
+    def offsets(self):
+        """{property name: byte offset in a row} of the properties the loader consumes"""
+        from . import _lib
+        return {name: int(self.layout.offset[k]) for k, name in enumerate(_lib.PLY_SLOT_NAMES) if self.layout.offset[k] >= 0}
+
+
+def ply_layout(filename):
+    """Where load_from_ply finds its properties in a PLY file's vertex rows (splat::ply_layout of libsplat_host.so): what
+    Renderer.upload_ply_rows / decode_ply_device take beside the rows.  A known name whose type is not float is absent; of
+    duplicated names the last wins."""
+    import ctypes as C
+    import os
+    from . import _lib
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libsplat_host.so")
+    if not os.path.exists(path):
+        raise RuntimeError("splat_amd: %s is missing -- run __graft_entry__.build()" % path)
+    L = C.CDLL(path)
+    L.splat_host_ply_layout.argtypes = [C.c_char_p, C.POINTER(_lib.PlyLayout), C.POINTER(C.c_int), C.POINTER(C.c_ulonglong),
+                                        C.POINTER(C.c_ulonglong), C.c_char_p, C.c_int]
+    L.splat_host_ply_layout.restype = C.c_int
+    lay, binary, off, nbytes = _lib.PlyLayout(), C.c_int(), C.c_ulonglong(), C.c_ulonglong()
+    err = C.create_string_buffer(512)
+    if L.splat_host_ply_layout(str(filename).encode(), C.byref(lay), C.byref(binary), C.byref(off), C.byref(nbytes), err, 512) != 0:
+        raise ValueError(err.value.decode("utf-8", "replace") or "ply_layout failed")
+    return PlyFileLayout(lay, binary.value, off.value, nbytes.value)
+
+
 def write_ply(filename, raw, n):
     """Write the 62-float INRIA layout (binary little endian).  raw: name -> array; missing -> 0."""
     dt = np.dtype([(p, "<f4") for p in PLY_PROPS])

@@ -20,7 +20,7 @@ def _fp(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
-def _device_address(a, what, floats, device):
+def _device_address(a, what, floats, device, any_dtype=False):
     """Device address of one scene buffer: an int is taken as it is; anything with data_ptr() (a torch tensor -- the
     package itself never imports torch) is checked as far as it describes itself: float32, contiguous, on the context's
     GPU, `floats` elements (None: not known yet)."""
@@ -31,7 +31,7 @@ def _device_address(a, what, floats, device):
     if not hasattr(a, "data_ptr"):
         raise TypeError("%s: expected a device address (int) or an object with data_ptr(), got %s" % (what, type(a).__name__))
     dt = getattr(a, "dtype", None)
-    if dt is not None and str(dt).rsplit(".", 1)[-1] != "float32":
+    if not any_dtype and dt is not None and str(dt).rsplit(".", 1)[-1] != "float32":
         raise TypeError("%s: float32 expected, got %s" % (what, dt))
     if hasattr(a, "is_contiguous") and not a.is_contiguous():
         raise ValueError("%s: not contiguous" % what)
@@ -159,6 +159,66 @@ class Renderer:
         st = _producer_stream(stream, (scales, rotations, out))
         self._check(self._L.splat_compute_cov3d_device(self._h, n, *[C.c_void_p(p) for p in ptrs], C.c_void_p(st)))
         return out
+
+    # ---- the scene from PLY rows ---------------------------------------------------------
+    @staticmethod
+    def _ply_layout_of(layout):
+        lay = getattr(layout, "layout", layout)                 # gaussians.ply_layout()'s result, or the structure itself
+        if not isinstance(lay, _lib.PlyLayout):
+            raise TypeError("layout: expected a _lib.PlyLayout (or gaussians.ply_layout()'s result), got %s" % type(layout).__name__)
+        return lay
+
+    def _ply_rows(self, rows, lay):
+        """device address of the vertex rows: an int, or anything with data_ptr() (a torch.uint8 tensor, say) -- of any
+        dtype, at any byte address, holding at least n * stride bytes where it can tell"""
+        p = _device_address(rows, "rows", None, int(self.config.device), any_dtype=True)
+        if not isinstance(rows, int) and hasattr(rows, "numel") and hasattr(rows, "element_size"):
+            have = int(rows.numel()) * int(rows.element_size())
+            if have < int(lay.n) * int(lay.stride):
+                raise ValueError("rows: %d bytes, the layout describes %d" % (have, int(lay.n) * int(lay.stride)))
+        return p
+
+    def load_ply(self, path, compute_cov3d=True):
+        """The scene from a PLY file, with the work on the GPU: the payload of a binary file crosses PCIe once, as the bytes
+        the file holds, and is decoded, activated, recentred and uploaded there (splat_upload_ply_device); an ascii file
+        takes the host loader and upload().  compute_cov3d=False leaves cov3d zero (Gaussian::new).  The frames are those of
+        load_from_ply + compute_cov3d + upload, byte for byte.  Returns the number of Gaussians."""
+        import os
+        so = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libsplat_host.so")
+        if not os.path.exists(so):
+            raise RuntimeError("splat_amd: %s is missing -- run __graft_entry__.build()" % so)
+        H = C.CDLL(so)
+        H.splat_host_load_ply_to_gpu.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_char_p, C.c_int]
+        H.splat_host_load_ply_to_gpu.restype = C.c_longlong
+        err = C.create_string_buffer(512)
+        n = H.splat_host_load_ply_to_gpu(self._h, str(path).encode(), 1 if compute_cov3d else 0, err, 512)
+        if n < 0:
+            raise ValueError(err.value.decode("utf-8", "replace") or "load_ply failed")
+        self.n = int(n)
+        return self.n
+
+    def upload_ply_rows(self, rows, layout, compute_cov3d=True, stream=None):
+        """splat_upload_ply_device: the scene from PLY vertex rows that are already in this GPU's memory.  rows: a device
+        address or an object with data_ptr(); layout: gaussians.ply_layout(path) or a _lib.PlyLayout; stream as in
+        upload_device.  Synchronous: `rows` is free again on return."""
+        lay = self._ply_layout_of(layout)
+        p = self._ply_rows(rows, lay) if lay.n else 0
+        st = _producer_stream(stream, (rows,))
+        self._check(self._L.splat_upload_ply_device(self._h, C.byref(lay), C.c_void_p(p), 1 if compute_cov3d else 0, C.c_void_p(st)))
+        self.n = int(lay.n)
+
+    def decode_ply_device(self, rows, layout, positions, scales, opacities, rotations, sh, stream=None):
+        """splat_decode_ply_device: PLY vertex rows in device memory -> five device buffers of the caller (positions [n,4],
+        scales [n,3], opacities [n], rotations [n,4] as (i,j,k,w), sh [n,48], float32), activated and recentred as
+        load_from_ply does.  Arguments and stream as in upload_device.  Returns when they are written."""
+        lay = self._ply_layout_of(layout)
+        n = int(lay.n)
+        dev = int(self.config.device)
+        ptrs = [_device_address(a, what, (per * n) if n else None, dev) for a, what, per in
+                ((positions, "positions", 4), (scales, "scales", 3), (opacities, "opacities", 1), (rotations, "rotations", 4), (sh, "sh", 48))]
+        p = self._ply_rows(rows, lay) if n else 0
+        st = _producer_stream(stream, (rows, positions, scales, opacities, rotations, sh))
+        self._check(self._L.splat_decode_ply_device(self._h, C.byref(lay), C.c_void_p(p), *[C.c_void_p(q) for q in ptrs], C.c_void_p(st)))
 
     def scene_layout(self):
         """(orig, bounds) of the current scene: orig[j] = the Gaussian stored in slot j (uint32 [n]); bounds = per K1 block
