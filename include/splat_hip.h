@@ -39,7 +39,8 @@ extern "C" {
 #define SPLAT_ABI_VERSION 7
 /* Added under version 7, with no change to any struct or earlier entry point: splat_decode_ply_device and
  * splat_upload_ply_device (and the splat_ply_layout they take).  A library of version 7 may predate them: a binding
- * that wants them finds them by symbol (dlsym / hasattr) and does without them where they are missing. */
+ * that wants them finds them by symbol (dlsym / hasattr) and does without them where they are missing.  Likewise
+ * splat_update_scene_device and splat_update_gaussians_device (and the SPLAT_FIELD_* bits they take). */
 
 /* modes: bit flags, 0 = the default */
 #define SPLAT_MODE_EXACT 0       /* back-to-front, 8-bit truncation per splat as blend() does it; the exponential of
@@ -175,6 +176,38 @@ int splat_decode_ply_device(splat_ctx* ctx, const splat_ply_layout* layout, cons
  * freed and the temporaries are gone.  n == 0: as splat_upload_scene_device with n == 0. */
 int splat_upload_ply_device(splat_ctx* ctx, const splat_ply_layout* layout, const void* d_rows, int32_t compute_cov3d,
                             void* producer_stream);
+
+/* The resident scene edited IN PLACE, n fixed: a training loop that shows its Gaussians every step, an editor that moves,
+ * hides or recolours a selection, a player of an animated scene.  Nothing is freed or allocated, nothing is sorted: the
+ * scene keeps the order of its last upload (splat_get_scene_layout's orig_out does not change) and only the named fields'
+ * values are rewritten.  A frame does not depend on that order, so the frames that follow are those of a fresh
+ * splat_upload_scene of the edited arrays, byte for byte; an order gone stale costs culling and binning efficiency
+ * (splat_stats.n_blocks_culled shows it), never a pixel -- upload again when it pays.  `fields`: */
+#define SPLAT_FIELD_POS 1      /* pos4    4 floats per row (x y z are stored; w is not read, as in the uploads) */
+#define SPLAT_FIELD_COV3D 2    /* cov3d   9 floats per row */
+#define SPLAT_FIELD_OPACITY 4  /* opacity 1 float per row  */
+#define SPLAT_FIELD_SH 8       /* sh      48 floats per row */
+/* Both calls are synchronous like the uploads (on return the inputs may be freed; producer_stream as for
+ * splat_upload_scene_device) and complete the frames in flight first: an asynchronous frame queued before the call shows
+ * the scene as it was.  A buffer whose field is not named is not read and may be NULL.  The K1 block bounds are recomputed
+ * from the resident values whenever POS or COV3D is named; the state kept from frame to frame (tile regions, sort launch
+ * sizes, the per-tile hints, the frame policy) starts over as after an upload.  splat_device_bytes() does not change,
+ * except that the first splat_update_gaussians_device on a scene makes the inverse of the order (4 bytes per Gaussian and
+ * one byte per block, kept until the scene is replaced).
+ * SPLAT_ERR_INVALID, before any device work: a NULL context, unknown bits in `fields`, a named field's pointer NULL with
+ * n or k > 0, k > 0 with a NULL d_index, k > n; SPLAT_ERR_NO_SCENE: no resident scene; SPLAT_ERR_INVALID: n is not the
+ * resident scene's.  fields == 0 or k == 0: SPLAT_OK, nothing done.
+ * The multi-GPU layer (splat_multi_*) has no counterpart yet: update each rank's context (splat_multi_ctx) yourself.
+ * splat_update_scene_device: the named fields of all n Gaussians from device buffers in splat_upload_scene's layouts,
+ * indexed by ORIGINAL Gaussian index. */
+int splat_update_scene_device(splat_ctx* ctx, uint64_t n, uint32_t fields, const void* d_pos4, const void* d_cov3d,
+                              const void* d_opacity, const void* d_sh, void* producer_stream);
+/* splat_update_gaussians_device: those fields of the k Gaussians d_index[0..k) (u32 original indices, distinct); the field
+ * buffers are COMPACT: row t belongs to Gaussian d_index[t].  Only the blocks that hold an edited Gaussian get new bounds.
+ * An index >= n: SPLAT_ERR_INVALID with nothing applied (the indices are checked on the device before anything is
+ * written).  Duplicate indices are the caller's error: which row lands is unspecified per field; nothing faults. */
+int splat_update_gaussians_device(splat_ctx* ctx, uint64_t k, const void* d_index, uint32_t fields, const void* d_pos4,
+                                  const void* d_cov3d, const void* d_opacity, const void* d_sh, void* producer_stream);
 
 /* Debug / stage parity: the stored scene order and K1 block bounds of the current scene.
  * orig_out: n u32 (slot j holds original Gaussian orig[j]); bounds_out: ceil(n/256) x 8 f32

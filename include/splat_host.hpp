@@ -83,6 +83,14 @@ PlyLayout ply_layout(const std::string& filename);
 // file goes through the host loader and splat_upload_scene.  compute_cov3d == false leaves cov3d zero (Gaussian::new).
 // Returns the number of Gaussians; the frames are those of the host path, byte for byte.
 uint64_t load_ply_to_gpu(splat_ctx* ctx, const std::string& filename, bool compute_cov3d = true);
+// The resident scene edited in place from DEVICE buffers (splat_update_scene_device, splat_update_gaussians_device):
+// `fields` = SPLAT_FIELD_* bits, a buffer whose field is not named may be null.  The whole-field form takes all n rows by
+// original index; the indexed form takes k compact rows, row t for Gaussian d_index[t] (u32, distinct).  The order of the
+// last upload stays; the frames are those of a fresh upload of the edited arrays.  Throws what the C call refuses.
+void update_scene_device(splat_ctx* ctx, uint64_t n, uint32_t fields, const void* d_pos4, const void* d_cov3d,
+                         const void* d_opacity, const void* d_sh, void* producer_stream = nullptr);
+void update_gaussians_device(splat_ctx* ctx, uint64_t k, const void* d_index, uint32_t fields, const void* d_pos4,
+                             const void* d_cov3d, const void* d_opacity, const void* d_sh, void* producer_stream = nullptr);
 
 struct GaussianList {           // src/gaussians.rs:408-416, SoA
     std::vector<float> positions;   // 4 x N (x,y,z,1)

@@ -13,6 +13,11 @@ pub const SPLAT_MODE_EXACT: i32 = 0;
 pub const SPLAT_MODE_CORRECTED_PROJECTION: i32 = 1;
 pub const SPLAT_MODE_LIBM_EXP: i32 = 2;
 pub const SPLAT_MODE_FAST: i32 = 4;
+// the fields an in-place edit names (splat_update_scene_device, splat_update_gaussians_device)
+pub const SPLAT_FIELD_POS: u32 = 1;
+pub const SPLAT_FIELD_COV3D: u32 = 2;
+pub const SPLAT_FIELD_OPACITY: u32 = 4;
+pub const SPLAT_FIELD_SH: u32 = 8;
 // tuning options (splat_set_option / splat_get_option): equivalent schedules and storage sizes, never pixels
 pub const SPLAT_OPT_PIPELINE_DEPTH: i32 = 1;
 pub const SPLAT_OPT_FUSED_SORT_MAX: i32 = 2;
@@ -108,6 +113,13 @@ extern "C" {
                                    producer_stream: *mut c_void) -> c_int;
     pub fn splat_upload_ply_device(ctx: *mut SplatCtx, layout: *const SplatPlyLayout, d_rows: *const c_void, compute_cov3d: i32,
                                    producer_stream: *mut c_void) -> c_int;
+    // the resident scene edited in place, n fixed (added under ABI 7, found by symbol like the two above): `fields` = SPLAT_FIELD_*
+    // bits, a buffer whose field is not named may be null; the indexed form takes k compact rows, row t for Gaussian d_index[t]
+    pub fn splat_update_scene_device(ctx: *mut SplatCtx, n: u64, fields: u32, d_pos4: *const c_void, d_cov3d: *const c_void,
+                                     d_opacity: *const c_void, d_sh: *const c_void, producer_stream: *mut c_void) -> c_int;
+    pub fn splat_update_gaussians_device(ctx: *mut SplatCtx, k: u64, d_index: *const c_void, fields: u32, d_pos4: *const c_void,
+                                         d_cov3d: *const c_void, d_opacity: *const c_void, d_sh: *const c_void,
+                                         producer_stream: *mut c_void) -> c_int;
     // debug / stage parity: the stored order (n u32) and the K1 block bounds (ceil(n/256) x 8 f32); either may be null
     pub fn splat_get_scene_layout(ctx: *mut SplatCtx, orig_out: *mut u32, n: u64, bounds_out: *mut f32, n_blocks: u64) -> c_int;
     pub fn splat_set_slab(ctx: *mut SplatCtx, tile_row0: i32, tile_row1: i32) -> c_int;

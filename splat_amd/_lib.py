@@ -41,6 +41,9 @@ class Record(C.Structure):
                 ("px0", C.c_int32), ("px1", C.c_int32), ("py0", C.c_int32), ("py1", C.c_int32)]
 
 
+# SPLAT_FIELD_*: the fields an in-place edit names (splat_update_scene_device, splat_update_gaussians_device)
+FIELD_POS, FIELD_COV3D, FIELD_OPACITY, FIELD_SH = 1, 2, 4, 8
+
 PLY_SLOTS = 59
 # destination slots of splat_ply_layout.offset: (first slot, count) per buffer, and the PLY property that feeds each slot
 PLY_SLOT_POS, PLY_SLOT_SCALE, PLY_SLOT_OPACITY, PLY_SLOT_ROT, PLY_SLOT_SH = 0, 3, 6, 7, 11
@@ -70,6 +73,9 @@ SYMBOLS = [
     ("splat_decode_ply_device", C.c_int, [C.c_void_p, C.POINTER(PlyLayout), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p]),
     ("splat_upload_ply_device", C.c_int, [C.c_void_p, C.POINTER(PlyLayout), C.c_void_p, C.c_int32, C.c_void_p]),
+    ("splat_update_scene_device", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("splat_update_gaussians_device", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p]),
     ("splat_get_scene_layout", C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint64, _fp, C.c_uint64]),
     ("splat_set_slab", C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     ("splat_tile_row_loads", C.c_int, [C.c_void_p, C.POINTER(CameraC), C.POINTER(C.c_uint64), C.c_int32]),

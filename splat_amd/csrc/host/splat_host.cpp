@@ -339,6 +339,19 @@ uint64_t load_ply_to_gpu(splat_ctx* ctx, const std::string& filename, bool compu
     return pl.layout.n;
 }
 
+void update_scene_device(splat_ctx* ctx, uint64_t n, uint32_t fields, const void* d_pos4, const void* d_cov3d,
+                         const void* d_opacity, const void* d_sh, void* producer_stream) {
+    if (!ctx) throw std::runtime_error("update_scene_device: no context");
+    check(splat_update_scene_device(ctx, n, fields, d_pos4, d_cov3d, d_opacity, d_sh, producer_stream), ctx, "splat_update_scene_device");
+}
+
+void update_gaussians_device(splat_ctx* ctx, uint64_t k, const void* d_index, uint32_t fields, const void* d_pos4,
+                             const void* d_cov3d, const void* d_opacity, const void* d_sh, void* producer_stream) {
+    if (!ctx) throw std::runtime_error("update_gaussians_device: no context");
+    check(splat_update_gaussians_device(ctx, k, d_index, fields, d_pos4, d_cov3d, d_opacity, d_sh, producer_stream), ctx,
+          "splat_update_gaussians_device");
+}
+
 // load_from_ply (src/gaussians.rs:375-405): the AoS `Vec<Gaussian>` the reference returns, from the same decode
 std::vector<Gaussian> load_from_ply(const std::string& filename) {
     GaussianList l = load_from_ply_soa(filename, 0);

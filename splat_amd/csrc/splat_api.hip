@@ -92,6 +92,11 @@ struct splat_ctx {
     BlockBounds* bounds = nullptr;         // per K1 block of 256 slots (block culling)
     bool cull_blocks = true;               // SPLAT_CULL=0 disables
     std::vector<unsigned int> h_orig;      // host copy of orig (ensure_h_orig: a device upload leaves it empty until a debug getter asks)
+    // in-place edits by index (splat_update_gaussians_device): ONE allocation, made by the first such call on a scene and
+    // freed with it -- inv[i] = the slot of Gaussian i (n words), the index check's counter, one dirty byte per K1 block
+    unsigned int* inv = nullptr;
+    unsigned int* upd_bad = nullptr;       // (inside inv's allocation)
+    unsigned char* upd_dirty = nullptr;    // (likewise)
     float ply_ms[3] = {0.0f, 0.0f, 0.0f};  // device time of decode, sum, subtract inside the most recent PLY decode
     float upload_sort_ms = 0.0f;           // device time of the sort inside the most recent splat_upload_scene_device
     // per-frame buffers
@@ -1254,6 +1259,7 @@ void fill_stats(splat_ctx* c, splat_stats* st) {
 
 void free_scene(splat_ctx* c) {
     dfree(c->planes); dfree(c->orig); dfree(c->bounds);
+    dfree(c->inv); c->upd_bad = nullptr; c->upd_dirty = nullptr;
     for (Slot& s : c->slots) { dfree(s.recs); dfree(s.depth); dfree(s.rect); dfree(s.vislist); dfree(s.blockinfo); dfree(s.large_list); dfree(s.large_count); s.used = false; }
     c->n = 0;
     c->h_orig.clear();
@@ -1752,6 +1758,108 @@ int splat_debug_upload_sort_ms(splat_ctx* c, double* ms) {
     *ms = c->upload_sort_ms;
     return SPLAT_OK;
 }
+
+}  // extern "C"
+
+namespace {
+// The two in-place edits (whole fields, by index) share everything but the repack and which blocks get new bounds.
+constexpr uint32_t FIELDS_ALL = SPLAT_FIELD_POS | SPLAT_FIELD_COV3D | SPLAT_FIELD_OPACITY | SPLAT_FIELD_SH;
+// what both refuse before they touch HIP (rows: n or k); nullptr: nothing
+const char* update_refusal(uint64_t rows, uint32_t fields, const void* pos4, const void* cov3d, const void* opacity, const void* sh) {
+    if (fields & ~FIELDS_ALL) return "unknown bits in fields";
+    if (rows && (((fields & SPLAT_FIELD_POS) && !pos4) || ((fields & SPLAT_FIELD_COV3D) && !cov3d) ||
+                 ((fields & SPLAT_FIELD_OPACITY) && !opacity) || ((fields & SPLAT_FIELD_SH) && !sh)))
+        return "NULL pointer for a named field";
+    return nullptr;
+}
+// update_begin: the frames in flight end as upload_begin ends them -- they show the scene as it was -- but the scene stays.
+// A frame found skipped stays pending for the next splat_sync, as for every call that quiesces on its way to something else.
+int update_begin(splat_ctx* c) {
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    int rc = finish_quiet(c);
+    if (rc != SPLAT_OK) return rc;
+    return sync_all(c);
+}
+// ... and update_finish: the per-scene state upload_finish resets, and nothing else -- other values under every tile
+void update_finish(splat_ctx* c) {
+    for (Slot& sl : c->slots) sl.layout_valid = false;
+    c->sort_hint = false;
+    if (c->need_hint && c->m_alloc) (void)fill_now(c->need_hint, 0, hint_table(c).bytes());
+    reset_policy(c);
+}
+// the inverse of the scene's order, the index check's counter and the dirty bytes: made by the first indexed edit of a scene
+hipError_t ensure_inverse(splat_ctx* c) {
+    if (c->inv) return hipSuccess;
+    const uint64_t n = c->n, nb = (n + 255) / 256;
+    hipError_t e = dmalloc(c, &c->inv, sizeof(unsigned int) * n + 16 + nb);
+    if (e != hipSuccess) return e;
+    c->upd_bad = c->inv + n;
+    c->upd_dirty = (unsigned char*)(c->inv + n) + 16;
+    if ((e = hipMemsetAsync(c->upd_bad, 0, 16 + nb, c->stream)) != hipSuccess) { dfree(c->inv); c->upd_bad = nullptr; c->upd_dirty = nullptr; return e; }
+    launch_inverse_order(c->stream, n, c->orig, c->inv);
+    return hipGetLastError();
+}
+}  // namespace
+
+extern "C" {
+
+#define UPD_TRY(expr)                                                           \
+    if ((e = (expr)) != hipSuccess)                                              \
+        return fail(c, SPLAT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e))
+
+int splat_update_scene_device(splat_ctx* c, uint64_t n, uint32_t fields, const void* d_pos4, const void* d_cov3d,
+                              const void* d_opacity, const void* d_sh, void* producer_stream) {
+    if (!c) return fail(c, SPLAT_ERR_INVALID, "NULL context");
+    if (const char* why = update_refusal(n, fields, d_pos4, d_cov3d, d_opacity, d_sh)) return fail(c, SPLAT_ERR_INVALID, why);
+    if (c->n == 0) return fail(c, SPLAT_ERR_NO_SCENE, "no resident scene to update");
+    if (n != c->n) return fail(c, SPLAT_ERR_INVALID, "n is not the resident scene's (changing n is an upload)");
+    if (fields == 0) return SPLAT_OK;
+    int rc = update_begin(c);
+    if (rc != SPLAT_OK) return rc;
+    hipError_t e;
+    UPD_TRY(follow_producer(c, producer_stream));
+    launch_repack_scene(c->stream, n, fields, (const float*)d_pos4, (const float*)d_cov3d, (const float*)d_opacity, (const float*)d_sh,
+                        c->orig, c->planes);
+    if (fields & (SPLAT_FIELD_POS | SPLAT_FIELD_COV3D)) launch_plane_bounds(c->stream, n, c->planes, nullptr, c->bounds);
+    UPD_TRY(hipGetLastError());
+    UPD_TRY(hipStreamSynchronize(c->stream));
+    update_finish(c);
+    return SPLAT_OK;
+}
+
+int splat_update_gaussians_device(splat_ctx* c, uint64_t k, const void* d_index, uint32_t fields, const void* d_pos4,
+                                  const void* d_cov3d, const void* d_opacity, const void* d_sh, void* producer_stream) {
+    if (!c) return fail(c, SPLAT_ERR_INVALID, "NULL context");
+    if (const char* why = update_refusal(k, fields, d_pos4, d_cov3d, d_opacity, d_sh)) return fail(c, SPLAT_ERR_INVALID, why);
+    if (k && !d_index) return fail(c, SPLAT_ERR_INVALID, "NULL index");
+    if (c->n == 0) return fail(c, SPLAT_ERR_NO_SCENE, "no resident scene to update");
+    if (k > c->n) return fail(c, SPLAT_ERR_INVALID, "more indices than Gaussians: they cannot be distinct");
+    if (fields == 0 || k == 0) return SPLAT_OK;
+    int rc = update_begin(c);
+    if (rc != SPLAT_OK) return rc;
+    const uint64_t n = c->n;
+    const unsigned int* index = (const unsigned int*)d_index;
+    hipError_t e;
+    UPD_TRY(ensure_inverse(c));
+    UPD_TRY(follow_producer(c, producer_stream));
+    // the indices first: the count of those that name no Gaussian comes back before anything is written
+    unsigned int bad = 0;
+    UPD_TRY(hipMemsetAsync(c->upd_bad, 0, sizeof(unsigned int), c->stream));
+    launch_index_check(c->stream, k, n, index, c->upd_bad);
+    UPD_TRY(hipGetLastError());
+    UPD_TRY(hipMemcpyAsync(&bad, c->upd_bad, sizeof bad, hipMemcpyDeviceToHost, c->stream));
+    UPD_TRY(hipStreamSynchronize(c->stream));
+    if (bad) return fail(c, SPLAT_ERR_INVALID, "an index is not below n; nothing was applied");
+    const bool rebound = (fields & (SPLAT_FIELD_POS | SPLAT_FIELD_COV3D)) != 0;
+    launch_repack_indexed(c->stream, n, k, index, fields, (const float*)d_pos4, (const float*)d_cov3d, (const float*)d_opacity,
+                          (const float*)d_sh, c->inv, c->planes, rebound ? c->upd_dirty : nullptr);
+    if (rebound) launch_plane_bounds(c->stream, n, c->planes, c->upd_dirty, c->bounds);
+    UPD_TRY(hipGetLastError());
+    UPD_TRY(hipStreamSynchronize(c->stream));
+    update_finish(c);
+    return SPLAT_OK;
+}
+#undef UPD_TRY
 
 }  // extern "C"
 

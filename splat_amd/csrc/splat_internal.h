@@ -158,6 +158,21 @@ void launch_block_bounds(hipStream_t s, uint64_t n, const float* pos4, const flo
 void launch_ply_decode(hipStream_t s, const splat_ply_layout& lay, const void* d_rows, float* pos4, float* scales3,
                        float* opacity, float* rot4, float* sh, float* mean, hipEvent_t* ev = nullptr);
 
+// A resident scene edited in place (splat_update.hip).  `fields`: SPLAT_FIELD_* bits; a buffer whose field is not named is
+// not read.  The order stays: the whole-field form reads row orig[j] for slot j, the indexed form writes slot
+// inv[index[t]] from row t of the compact buffers (inv: launch_inverse_order) and marks the blocks it touched in `dirty`
+// (one byte per K1 block, nullptr: not wanted).  launch_index_check adds to *bad the indices that are >= n.
+void launch_inverse_order(hipStream_t s, uint64_t n, const unsigned int* orig, unsigned int* inv);
+void launch_index_check(hipStream_t s, uint64_t k, uint64_t n, const unsigned int* index, unsigned int* bad);
+void launch_repack_scene(hipStream_t s, uint64_t n, uint32_t fields, const float* pos4, const float* cov3d, const float* opacity,
+                         const float* sh, const unsigned int* orig, float4* planes);
+void launch_repack_indexed(hipStream_t s, uint64_t n, uint64_t k, const unsigned int* index, uint32_t fields, const float* pos4,
+                           const float* cov3d, const float* opacity, const float* sh, const unsigned int* inv, float4* planes,
+                           unsigned char* dirty);
+// ... and the bounds of the K1 blocks from the planes, as block_bounds computes them from the buffers; dirty != nullptr:
+// only the blocks whose byte is set, which is cleared
+void launch_plane_bounds(hipStream_t s, uint64_t n, const float4* planes, unsigned char* dirty, BlockBounds* bounds);
+
 // ---- The per-frame launches take one argument block each, by const&.  The blocks are plain aggregates without defaults: a
 // caller value-initialises one (`ScanArgs a{};`) and what it does not set is zero / nullptr / false.  What travels together
 // is a sub-struct:

@@ -69,7 +69,7 @@ class DeviceGaussians:
         return p
 
     def update(self, field, array):
-        """overwrite one buffer from a host array of the same size (an edit of the scene in place)"""
+        """overwrite one buffer from a host array of the same size (an edit of the scene in place: refresh() shows it)"""
         import ctypes as C
         a = np.ascontiguousarray(array, f32)
         if field not in self.FIELDS or not getattr(self, field):
@@ -85,6 +85,17 @@ class DeviceGaussians:
     def upload(self):
         """make this the renderer's scene (Renderer.upload_device)"""
         self._r.upload_device(self.positions, self.cov3d, self.opacities, self.sh, n=self.n)
+        return self
+
+    def refresh(self, *fields):
+        """show the renderer these buffers as they are now, in place (Renderer.update_device): the named ones among
+        "positions", "cov3d", "opacities", "sh", all four when none is named.  The renderer's scene must be this one
+        (upload() first); its order stays, its frames are those of upload() of the same values."""
+        shown = ("positions", "cov3d", "opacities", "sh")
+        for f in fields:
+            if f not in shown:
+                raise ValueError("refresh: %r is not one of %s" % (f, ", ".join(shown)))
+        self._r.update_device(n=self.n, **{f: getattr(self, f) for f in (fields or shown)})
         return self
 
     def free(self):

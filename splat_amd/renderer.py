@@ -149,6 +149,47 @@ class Renderer:
         self._check(self._L.splat_upload_scene_device(self._h, n, *[C.c_void_p(p) for p in ptrs], C.c_void_p(st)))
         self.n = n
 
+    def _update_fields(self, rows, positions, cov3d, opacities, sh):
+        """(mask, [four addresses]) of an in-place edit of `rows` rows: a field that is None is not named and its address 0"""
+        dev = int(self.config.device)
+        mask, ptrs = 0, []
+        for a, what, per, bit in ((positions, "positions", 4, _lib.FIELD_POS), (cov3d, "cov3d", 9, _lib.FIELD_COV3D),
+                                  (opacities, "opacities", 1, _lib.FIELD_OPACITY), (sh, "sh", 48, _lib.FIELD_SH)):
+            if a is None:
+                ptrs.append(0)
+            else:
+                mask |= bit
+                ptrs.append(_device_address(a, what, per * rows, dev))
+        return mask, ptrs
+
+    def update_device(self, positions=None, cov3d=None, opacities=None, sh=None, stream=None, n=None):
+        """splat_update_scene_device: the resident scene edited in place.  The fields that are not None are rewritten for all
+        n Gaussians from device buffers (layouts, addresses and stream as in upload_device, indexed by original Gaussian); the
+        others stay.  Nothing is freed, allocated or sorted: the scene keeps the order of its last upload, and the frames
+        that follow are those of upload() of the edited arrays, byte for byte.  Synchronous; frames in flight end first and
+        show the scene as it was."""
+        n = self.n if n is None else int(n)
+        mask, ptrs = self._update_fields(n, positions, cov3d, opacities, sh)
+        st = _producer_stream(stream, (positions, cov3d, opacities, sh))
+        self._check(self._L.splat_update_scene_device(self._h, n, mask, *[C.c_void_p(p) for p in ptrs], C.c_void_p(st)))
+
+    def update_indexed(self, index, positions=None, cov3d=None, opacities=None, sh=None, stream=None, k=None):
+        """splat_update_gaussians_device: the same for the k Gaussians index[0..k) (uint32 / int32 original indices in device
+        memory, distinct; k= with a plain address).  The field buffers are compact: row t belongs to Gaussian index[t].  An
+        index >= n raises SplatError(ERR_INVALID) with nothing applied."""
+        if k is None:
+            if isinstance(index, int) or not hasattr(index, "numel"):
+                raise TypeError("k= is required with a plain device address")
+            k = int(index.numel())
+        k = int(k)
+        if not isinstance(index, int) and hasattr(index, "element_size") and int(index.element_size()) != 4:
+            raise TypeError("index: 32-bit indices expected, got %s" % getattr(index, "dtype", None))
+        pi = _device_address(index, "index", k, int(self.config.device), any_dtype=True)
+        mask, ptrs = self._update_fields(k, positions, cov3d, opacities, sh)
+        st = _producer_stream(stream, (index, positions, cov3d, opacities, sh))
+        self._check(self._L.splat_update_gaussians_device(self._h, k, C.c_void_p(pi), mask, *[C.c_void_p(p) for p in ptrs],
+                                                          C.c_void_p(st)))
+
     def compute_cov3d_device(self, scales, rotations, out, stream=None, n=None):
         """splat_compute_cov3d_device: kernel K0 from device buffers (scales [n,3], rotations [n,4]) into a device buffer
         (out [n,9]); arguments and stream as in upload_device.  Returns when `out` is written."""
