@@ -1,5 +1,7 @@
 // splat_api.hip -- C ABI (include/splat_hip.h) over the gfx950 kernels.  Host side only:
 // buffer ownership, per-frame constants, launch sequence, HIP-event timing, error reporting.
+// The entry points that put values into the resident scene (uploads, PLY, edits, K0) are splat_scene.hip's; the context both
+// files share is splat_context.h.
 //
 // Frames overlap on the device (SPLAT_PIPELINE): per-frame buffers live in SLOTS used in rotation; preprocess +
 // scan + sort of later frames run on internal high-priority streams into the next slots while frame N composites
@@ -21,233 +23,13 @@
 #include <unordered_map>
 #include <vector>
 
-#include "splat_internal.h"
-#include "../../include/splat_policy.h"
+#include "splat_context.h"
 
 using namespace splat;
 
-namespace {
-thread_local std::string g_create_error;
-constexpr int N_EV = 9;        // e0..e2 on the bin stream (start, K1, scan), e8, e3, e4 on the sort stream (start, K2, K3), e5..e7 on the caller's (K4 start, K4 end, status)
-constexpr int N_TIMES = 6;     // preprocess, scan, emit, sort, composite, status read-back
-constexpr int EV_RING = 32;
-static_assert(EV_RING == SPLAT_POLICY_RING, "the frame policy sees the whole status ring");
-constexpr int N_SLOTS = 4;
-
-struct EvSet {
-    hipEvent_t e[N_EV];
-    bool used = false;
-    bool timed = false;        // the per-kernel events e0..e6, e8 were recorded for this frame
-};
-
-struct Slot {                  // everything one frame writes before the image
-    Rec* recs = nullptr;
-    float* depth = nullptr;
-    ushort4* rect = nullptr;
-    unsigned int* vislist = nullptr;
-    unsigned int* counts = nullptr;        // per tile: pair count (two-pass binning, zero between frames) / cursor of the tile's region (one-pass)
-    unsigned int* counts_b = nullptr;      // one-pass binning: cursors and regions exist twice per slot -- the layout of the slot's NEXT frame
-    unsigned int* lay_a = nullptr;         // is written (layout_kernel of an earlier frame on the same stream) while nothing reads that copy
-    unsigned int* lay_b = nullptr;
-    int flip = 0;                          // which copy the slot's next frame uses (0: counts / lay_a, 1: counts_b / lay_b)
-    bool layout_valid = false;             // ... and whether it holds regions for the current scene / target / slab
-    unsigned int* offsets = nullptr;
-    unsigned int* cursor = nullptr;
-    unsigned int* order = nullptr;
-    unsigned int* lens = nullptr;           // list length per tile (the list starts at offsets[tile])
-    // Binning again on the device (overflow redo): counters, regions and cursors of a frame whose lists outgrew the regions
-    // it was given -- its second binning pass writes here, not into the copies the pipeline hands on
-    unsigned int* redo_layout = nullptr;
-    unsigned int* redo_cursors = nullptr;
-    uint64_t layout_cam[2] = {0, 0};        // per copy of the layout: a hash of the camera whose lists sized it
-    unsigned int* near_m = nullptr;         // near selection: per tile, how many of its list's nearest keys launch_select put in order
-    unsigned long long* keys = nullptr;
-    unsigned long long* keys2 = nullptr;   // the second key buffer: sorted near selections, scatter space of the long lists' sorts and merges
-    unsigned int* off2 = nullptr;          // one-pass binning: per tile, where its room in keys2 starts (handed out by the frame's scan to the
-                                           // lists of more than 2048 keys; two-pass binning mirrors the first buffer instead)
-    unsigned int* blockinfo = nullptr;     // per K1 block: the info word this slot's last K1 wrote (see launch_preprocess);
-                                           // per slot, because the K1s of consecutive frames run concurrently
-    uint4* large_list = nullptr;           // one-pass binning: the frame's large splats (key, tile rectangle), n entries -- K1 lists them,
-    unsigned int* large_count = nullptr;   // bin_large_kernel bins them tile by tile; the counter is zero between frames (scan / layout reset it)
-    FrameStatus* d_status = nullptr;
-    hipEvent_t ev_binned = nullptr;        // bin stream -> sort stream: buckets and lengths are final
-    hipEvent_t ev_ready = nullptr;         // sort stream -> caller's stream: lists are sorted
-    int free_ring = -1;                    // compositor's stream -> bin stream: the slot is free when the frame that used it last has
-                                           // ended -- that frame's ring event (an event of the slot's own would be a second barrier
-                                           // packet behind every compositor: ~3 us of queue drain per frame)
-    bool used = false;
-};
-}  // namespace
-
-struct splat_ctx {
-    splat_config cfg{};
-    hipStream_t stream = nullptr;          // compositor + image: the caller-visible stream
-    bool own_stream = false;
-    hipStream_t bin_stream = nullptr;      // K1 + scan of a later frame
-    hipStream_t sort_stream = nullptr;     // K2 + K3 (depth 2: the bin stream itself)
-    // scene
-    uint64_t n = 0;
-    float4* planes = nullptr;
-    unsigned int* orig = nullptr;          // slot -> original Gaussian index (Morton order of position)
-    BlockBounds* bounds = nullptr;         // per K1 block of 256 slots (block culling)
-    bool cull_blocks = true;               // SPLAT_CULL=0 disables
-    std::vector<unsigned int> h_orig;      // host copy of orig (ensure_h_orig: a device upload leaves it empty until a debug getter asks)
-    // in-place edits by index (splat_update_gaussians_device): ONE allocation, made by the first such call on a scene and
-    // freed with it -- inv[i] = the slot of Gaussian i (n words), the index check's counter, one dirty byte per K1 block
-    unsigned int* inv = nullptr;
-    unsigned int* upd_bad = nullptr;       // (inside inv's allocation)
-    unsigned char* upd_dirty = nullptr;    // (likewise)
-    float ply_ms[3] = {0.0f, 0.0f, 0.0f};  // device time of decode, sum, subtract inside the most recent PLY decode
-    float upload_sort_ms = 0.0f;           // device time of the sort inside the most recent splat_upload_scene_device
-    // per-frame buffers
-    Slot slots[N_SLOTS];
-    unsigned int m_alloc = 0;
-    uint64_t cap = 0;                      // entries in each used slot's keys buffer
-    uint64_t cap2 = 0;                     // entries in each used slot's second key buffer (0: none).  Two-pass binning: a mirror of the first
-                                           // (cap2 == cap); one-pass: room for the lists of more than 2048 keys only (default_keys2_capacity)
-    uint64_t keys2_want = 0;               // a harvested frame's long lists outgrew the second key buffer: grow to this
-    // one-pass binning (per-tile regions of the key buffer, sized from earlier frames' lists): on unless SPLAT_BUCKETS=0, the
-    // caller fixed pair_capacity, or the key buffers would not fit bucket_bytes
-    bool use_buckets = true;
-    bool bucket_failed = false;            // sticky until the scene changes
-    uint64_t bucket_bytes = 128ull << 30;  // SPLAT_BUCKET_BYTES: all key buffers of all slots together (288 GB of HBM per GPU)
-    uint64_t layout_want = 0;              // entries the regions of a harvested frame asked for and did not get (grow to this)
-    unsigned int layout_m = 0;             // tile count the slots' layouts were built for
-    bool last_one_pass = false;            // what the previous frame's binning was (the cursors must be zero for two-pass counting)
-    unsigned int* zero_layout = nullptr;   // m_alloc zeros: the empty layout of the bootstrap (every key dropped, every pair counted)
-    uint64_t dev_bytes = 0, dev_bytes_peak = 0;   // device memory held by this context
-    LaunchKnobs knobs;                     // experiment switches of the launch wrappers (this context's)
-    float region_spare = 4.0f;             // SPLAT_REGION_SPARE: how far a tile's region may grow into the key buffer's spare room (1: not at all)
-    uint64_t frame_idx = 0;
-    int last_slot = -1;                    // buffer slot of the most recent frame (debug getters)
-    bool last_lists_in_memory = false;     // ... and whether its compositor wrote the lists it sorted back to the buckets
-    FrameStatus* h_status = nullptr;       // pinned, one per event-ring entry
-    // Every frame in flight has a device status of its own (one per event-ring entry).  The scan kernel -- where a
-    // frame's pair count, longest list and every overflow verdict are decided -- initialises it and writes the same
-    // words straight into the pinned host copy, so an asynchronous frame needs no read-back and no reset on any
-    // stream: the caller's stream carries nothing but the compositors back to back (a copy and two fills used to sit
-    // between them, ~30 us per frame; a side stream for them shares a hardware queue with a binning stream and
-    // serialises the frames).  Frames rendered with statistics still copy the final status (late counters).
-    FrameStatus* d_status_ring = nullptr;
-    bool clear_first = false;              // the frame being enqueued starts from a cleared image (fused into the compositor)
-    // host-image path
-    uint32_t* d_img = nullptr;
-    size_t img_cap = 0;
-    // streaming path (splat_render_stream): two device images, a copy stream, per-image events
-    static constexpr int S_IMGS = 4;       // streamed frames in flight (device images): the pipeline wants three (two chains + a compositor)
-    uint32_t* s_img[S_IMGS] = {};
-    size_t s_cap = 0;
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t s_rendered[S_IMGS] = {}, s_copied[S_IMGS] = {};
-    const uint32_t* s_dst[S_IMGS] = {};
-    bool s_used[S_IMGS] = {};
-    uint64_t s_idx = 0;
-    int s_ring[S_IMGS] = {-1, -1, -1, -1}; // event-ring entry of the frame each streaming image holds
-    splat_camera s_cam[S_IMGS] = {};       // ... and its camera (a frame skipped on the device is redone by splat_stream_wait)
-    // slab
-    int slab0 = 0, slab1 = -1;
-    // timing
-    EvSet ring[EV_RING];
-    int ring_next = 0;
-    int last_ring = -1;
-    double acc_ms[N_TIMES] = {0, 0, 0, 0, 0, 0};
-    uint64_t acc_frames = 0;
-    // last frame
-    FrameConst fc{};
-    unsigned int n_tiles = 0;
-    uint64_t overflow_want = 0;            // a harvested frame overflowed the pair buffer: grow to this
-    bool bucket_overflow = false;          // a harvested frame overflowed a tile bucket: leave one-pass binning
-    // sort launch sizes: the long-list sort launches cover a prefix of the longest-first tile order,
-    // sized from the most recent harvested frame (+25 % + slack); the device validates, a miss redoes the frame
-    bool sort_hint = false, sort_grid_miss = false;
-    unsigned int hint_ge8192 = 0, hint_ge2048 = 0, hint_ge16384 = 0;
-    // which flavour of the exact walk the compositor runs (the pixels are the same): 0 = one record per step, 1 = two
-    // records per step with packed math (fewer issue slots: for frames whose compositor is bound by its longest
-    // list's single wave, not by throughput), -1 = by the last harvested frame's pairs per key of the longest list
-    int pair_mode = -1;                    // SPLAT_PAIR_BLEND
-    uint64_t hint_pairs = 0; unsigned int hint_maxlen = 0; unsigned int hint_large = 0, hint_window = 0;
-    unsigned int grid_big = 0, grid_mid = 0, grid_long = 0;      // what the frame being enqueued uses
-    FrameStatus last{};
-    // frames skipped on the device (their storage outgrown: see finish_frame).  A synchronous call redoes its own
-    // frame; a lost ASYNCHRONOUS frame is reported once, by the next splat_sync / splat_stream_wait
-    uint64_t frames_dropped = 0, frames_drop_reported = 0;
-    bool deferred_drop = false;
-    bool tight_grids = false;              // SPLAT_DBG_TIGHT_GRIDS: sort launches sized with no margin (tests force a miss)
-    uint2* d_iters = nullptr;              // per compositor wave: (scan, blend) iterations of a frame rendered with stats
-    unsigned int iters_alloc = 0;
-    bool iters_valid = false;
-    // Who sorts the lists of more than 2048 keys: 0 = the sort launches (74 / 147 KB workgroups, starved beside a compositor
-    // in flight, but the cheaper code), 1 = the tile's own compositor workgroup (no launches, no starvation, more
-    // work), -1 = by the previous frame: the compositor when the AVERAGE list is longer than 2048 keys, i.e. when
-    // the sort launches would carry most of the frame's keys, and the frame is throughput-bound (C5: +7 %; C3 -5 %, C2 -13 %
-    // if forced).  SPLAT_SORT_IN_COMP.
-    int sort_in_comp = -1;
-    float fast_width = 2.0f;               // SPLAT_MODE_FAST: bracket width that counts as closed (SPLAT_FAST_WIDTH: 1 or 2)
-    float early_eps = 1e-6f;               // SPLAT_EARLY_EPS overrides (0 disables the early-out)
-    int early_min = 768;                   // SPLAT_EARLY_MIN
-    int early_scan8 = 4;                   // SPLAT_EARLY_SCAN8
-    int prio_len = 0x3fffffff;             // SPLAT_PRIO_LEN
-    unsigned int fused_sort_max = 2048;    // SPLAT_FUSED_SORT: lists up to this length are sorted inside the compositor (0: off)
-    // Near selection (SPLAT_NEAR_KEYS / SPLAT_OPT_NEAR_SELECT_KEYS; 0 = off): a list of more than 2048 keys is not sorted; its
-    // tile's compositor workgroup selects the nearest <= near_cap keys by depth and sorts those -- the exact early-out never
-    // looks farther on all but a few tiles, which then sort their whole list after all.  No sort launches in such frames.
-    unsigned int near_cap = 2048;
-    // Overflow redo (SPLAT_OVERFLOW_REDO / SPLAT_OPT_OVERFLOW_REDO, default on): a frame whose camera differs from the one its
-    // tile regions were sized for carries a second binning (count pass, exact regions, K1, scan) behind its scan, as launches
-    // that leave at once unless that scan found a tile beyond its region -- such a frame is binned again on the device
-    // instead of being skipped, reported and rendered again by the caller.
-    // 0 = off; 1 = ADAPTIVE (default): the redo launches ride on moving frames only while a list has outgrown its region within
-    // the last 256 frames (a scene that never does -- most -- pays nothing; the first such frame after a quiet stretch is
-    // skipped and reported as before, and arms the redo); 2 = on every moving frame.
-    int overflow_redo = 1;
-    // What the frame policy (include/splat_policy.h, splat_policy.cpp: a pure function, tested without a GPU) carries from frame
-    // to frame: the previous camera and how long it has been the same, the count-first / overflow-redo runs left, how the frames
-    // in the status ring were binned.  reset_policy() where the lists it speaks of stop existing (scene, target, slab, options).
-    splat_policy_state pol{};
-    // One-pass binning: splats of more tiles than this (and every splat wider or taller than K1's 32 x 32-tile window) go to the
-    // frame's large list and are binned tile by tile behind K1 (bin_large_kernel).  SPLAT_LARGE_TILES: 0 = the window alone
-    // decides, < 0 = no list at all (K1's blocks expand close-ups themselves, one atomic per pair: the round-5 path).
-    int layout_motion = 1;               // SPLAT_LAYOUT_MOTION=0: regions always sized from each tile's own list (round 6)
-    int large_list_min = 256;            // SPLAT_LARGE_LIST_MIN: large splats a recent frame must have had for frames to keep the list (splat_policy.h)
-    int large_tiles = 128;               // (C2 / C3 / C5, bench pose and from inside: 96-128 best of 0..1024, profiles/r07_large_splats.txt)
-    int count_first = 1;                   // SPLAT_OPT_COUNT_FIRST: 0 only slots without a layout; 1 + the 64 moving frames behind a run of frames that outgrew
-                                           // their regions (three in four of the recent ones); 2 + every frame whose camera moved by more than half a degree
-    bool idle = false;                     // nothing of this context is in flight (set by the waits that drain every stream, cleared by every enqueue)
-    int start_hints = 2;                   // SPLAT_OPT_START_HINTS / SPLAT_START_HINTS: 0 the compositor scans for its walks' starts on every frame; 1 not with
-                                           // a camera at rest; 2 nor, three frames of four, with one in slow motion (see enqueue_frame)
-    bool one_pass_select = true;           // SPLAT_DBG_ONE_PASS_SELECT=0: near selection always takes its two passes (histogram, compaction)
-    int start_refine = 1;                  // SPLAT_OPT_START_REFINE / SPLAT_START_REFINE: a camera at rest refines its walks' starts (splat_policy_decision::refine)
-    unsigned int* need_hint = nullptr;     // the per-tile hint table (HintTable of splat_internal.h, m_alloc words a plane: hint_table() below): first in
-                                           // it, per tile and wave, the nearest keys its walk needed in the most recent frame
-    bool last_near = false;                // the most recent frame ran with near selection: its long lists are unordered in memory
-    int timing_every = 8;                  // SPLAT_TIMING_EVERY: per-kernel events on every n-th frame (and whenever stats are asked for)
-    int pipeline = 6;                      // frames in flight on the device (SPLAT_PIPELINE = 1..6, see enqueue_frame)
-    // Compositor LANES (splat_set_frame_overlap): the compositors of consecutive frames run one after the other on the
-    // context's stream (lane 0) -- unless overlap is on and the frames go to DIFFERENT images (a swap chain), in which case
-    // the second lane (the copy stream: ensure_lane) takes every other one and two compositors share the chip.  A frame that is
-    // bound by the latency of its densest tile's lone wave (small scenes, multi-GPU slabs) leaves the chip mostly idle:
-    // with two lanes C2 runs at 7.9 k instead of 5.7 k frames/s, an eighth-of-a-frame slab at 0.08 instead of 0.13 ms.
-    // lane[q]: its most recent frame (sequence number, event-ring entry).  img_tab: the most recent frame of every image
-    // seen lately (address range, lane, ring entry) -- hazards are decided per IMAGE: with three images in rotation the
-    // earlier frame to an image is not its lane's last one.
-    struct Lane { uint64_t seq = 0; int ring = -1; };
-    Lane lane[2];
-    struct ImgRec { const char* lo = nullptr; const char* hi = nullptr; uint64_t seq = 0; int ring = -1; int lane = 0; };
-    static constexpr int N_IMG_TAB = 8;
-    ImgRec img_tab[N_IMG_TAB];
-    hipStream_t comp2 = nullptr;           // lane 1 (lane 0 is `stream`)
-    int overlap = 1;                       // splat_set_frame_overlap / SPLAT_FRAME_OVERLAP: 2 = asynchronous frames may use lane 1
-    int last_lane = 0;                     // the lane of the most recent frame
-    uint64_t lane_seq = 0;
-    bool streamed_call = false;            // splat_render_stream is rendering: its frames stay on lane 0 (lane 1's stream carries their copies)
-    hipEvent_t pre_wait = nullptr;         // one-shot: the next frame's compositor waits for it (splat_render_stream: its image is still crossing PCIe)
-    uint32_t env_pinned = 0;               // bit k: SPLAT_OPT_k was set from the environment at splat_create (splat_set_option leaves it alone)
-    int host_zero_copy = 1;                // SPLAT_OPT_HOST_ZERO_COPY: splat_render_frame's compositor stores into a device-addressable host image
-    uint64_t region_mult = 0;              // the key buffer's entries per Gaussian chosen for this scene (0: not yet)
-    unsigned int keys_per_gaussian = 0;    // SPLAT_OPT_KEYS_PER_GAUSSIAN: 0 = default_region_capacity decides
-    splat::CommState* comm = nullptr;      // multi-GPU: RCCL communicator + partition (splat_multi.hip)
-    std::string err;
-};
+static thread_local std::string g_create_error;
+static std::mutex g_ledger_mu;
+static std::unordered_map<void*, std::pair<splat_ctx*, size_t>> g_ledger;      // device allocation -> (context, bytes)
 
 namespace splat {
 CommState** ctx_comm_slot(splat_ctx* c) { return &c->comm; }
@@ -266,108 +48,28 @@ int frame_tail(splat_ctx* c) {
 }
 int ctx_device(const splat_ctx* c) { return c->cfg.device; }
 int ctx_fail(splat_ctx* c, int code, const char* msg) { if (c) c->err = msg; return code; }
-}  // namespace splat
 
-namespace {
-
-#define HIP_TRY(ctx, expr)                                                                             \
-    do {                                                                                               \
-        hipError_t _e = (expr);                                                                        \
-        if (_e != hipSuccess) {                                                                        \
-            (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(_e);                            \
-            return SPLAT_ERR_HIP;                                                                      \
-        }                                                                                              \
-    } while (0)
-
+// (splat_context.h: both host files report and account through these)
 int fail(splat_ctx* ctx, int code, const std::string& msg) {
     if (ctx) ctx->err = msg; else g_create_error = msg;
     return code;
 }
+void ledger_add(splat_ctx* c, void* p, size_t bytes) {
+    std::lock_guard<std::mutex> g(g_ledger_mu);
+    g_ledger[p] = {c, bytes};
+    c->dev_bytes += bytes;
+    c->dev_bytes_peak = std::max(c->dev_bytes_peak, c->dev_bytes);
+}
+void ledger_del(void* p) {
+    std::lock_guard<std::mutex> g(g_ledger_mu);
+    auto it = g_ledger.find(p);
+    if (it == g_ledger.end()) return;
+    it->second.first->dev_bytes -= it->second.second;
+    g_ledger.erase(it);
+}
+}  // namespace splat
 
-// Upload-time ordering: 30-bit Morton code of the position inside the scene's bounding box.
-// order[j] = original index stored in slot j.  Ties keep index order; non-finite positions go first.
-inline uint32_t spread3(uint32_t v) {
-    v &= 0x3ffu;
-    v = (v | (v << 16)) & 0x030000ffu;
-    v = (v | (v << 8)) & 0x0300f00fu;
-    v = (v | (v << 4)) & 0x030c30c3u;
-    v = (v | (v << 2)) & 0x09249249u;
-    return v;
-}
-void morton_order(uint64_t n, const float* pos4, std::vector<unsigned int>& order) {
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (uint64_t i = 0; i < n; ++i)
-        for (int a = 0; a < 3; ++a) {
-            float v = pos4[4 * i + a];
-            if (std::isfinite(v)) { lo[a] = std::min(lo[a], v); hi[a] = std::max(hi[a], v); }
-        }
-    float sc[3];
-    for (int a = 0; a < 3; ++a) sc[a] = (hi[a] > lo[a]) ? 1023.0f / (hi[a] - lo[a]) : 0.0f;
-    std::vector<uint64_t> keyed(n);
-    for (uint64_t i = 0; i < n; ++i) {
-        uint32_t code = 0;
-        for (int a = 0; a < 3; ++a) {
-            float v = pos4[4 * i + a];
-            uint32_t q = std::isfinite(v) ? (uint32_t)std::min(1023.0f, std::max(0.0f, (v - lo[a]) * sc[a])) : 0u;
-            code |= spread3(q) << a;
-        }
-        keyed[i] = ((uint64_t)code << 32) | (uint64_t)i;
-    }
-    std::sort(keyed.begin(), keyed.end());
-    order.resize(n);
-    for (uint64_t j = 0; j < n; ++j) order[j] = (unsigned int)keyed[j];
-}
-
-// Bounds of every K1 block (256 consecutive slots): AABB of the finite centres, largest ||cov3d||_F.
-void block_bounds(uint64_t n, const float* pos4, const float* cov3d, const std::vector<unsigned int>& order,
-                  std::vector<BlockBounds>& out) {
-    const uint64_t nb = (n + 255) / 256;
-    out.resize(nb);
-    for (uint64_t b = 0; b < nb; ++b) {
-        BlockBounds bb;
-        for (int a = 0; a < 3; ++a) { bb.lo[a] = INFINITY; bb.hi[a] = -INFINITY; }
-        bb.fmax = 0.0f; bb.pad = 0.0f;
-        const uint64_t j1 = std::min<uint64_t>(n, (b + 1) * 256);
-        for (uint64_t j = b * 256; j < j1; ++j) {
-            const uint64_t i = order[j];
-            const float* p = pos4 + 4 * i;
-            if (!(std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]))) continue;   // never visible
-            for (int a = 0; a < 3; ++a) { bb.lo[a] = std::min(bb.lo[a], p[a]); bb.hi[a] = std::max(bb.hi[a], p[a]); }
-            double f2 = 0.0;
-            for (int e = 0; e < 9; ++e) f2 += (double)cov3d[9 * i + e] * (double)cov3d[9 * i + e];
-            float f = (float)std::sqrt(f2) * 1.0001f;
-            if (!(f >= 0.0f)) f = INFINITY;                    // NaN: unbounded extent
-            bb.fmax = std::max(bb.fmax, f);
-        }
-        if (!(bb.lo[0] <= bb.hi[0]))                            // no finite centre at all: NaN bounds answer "maybe"
-            for (int a = 0; a < 3; ++a) { bb.lo[a] = NAN; bb.hi[a] = NAN; }
-        out[b] = bb;
-    }
-}
-
-// Device allocations of a context go through these two, so that splat_device_bytes() can say what it holds (sizes are
-// kept in a side table: hipFree does not tell).
-void ledger_add(splat_ctx* c, void* p, size_t bytes);
-void ledger_del(void* p);
-template <typename T>
-hipError_t dmalloc(splat_ctx* c, T** p, size_t bytes) {
-    hipError_t e = hipMalloc(p, bytes);
-    if (e == hipSuccess) ledger_add(c, (void*)*p, bytes);
-    return e;
-}
-template <typename T>
-void dfree(T*& p) {
-    if (p) { ledger_del((void*)p); (void)hipFree(p); p = nullptr; }
-}
-
-// hipMemset on device memory is ENQUEUED (on the legacy default stream) and may return before the fill has run -- and the
-// context's streams are non-blocking: nothing on them waits for that stream.  A fill that the next launches depend on is
-// waited for here.  (Found with eight processes on one GPU, where the default stream's fill arrives late: the first
-// splat_tile_row_loads of two ranks in eight counted into counters that were zeroed afterwards -- tools/row_loads_stress.py.)
-hipError_t fill_now(void* p, int value, size_t bytes) {
-    hipError_t e = hipMemset(p, value, bytes);
-    return e == hipSuccess ? hipStreamSynchronize(nullptr) : e;
-}
+namespace {
 
 const float* ev_times(const EvSet& s, float t[N_TIMES]) {
     static const int pairs[N_TIMES][2] = {{0, 1}, {1, 2}, {8, 3}, {3, 4}, {5, 6}, {6, 7}};
@@ -399,22 +101,6 @@ void harvest(splat_ctx* c, int r) {
     if (st.overflow == 0 || st.overflow == 3) { c->sort_hint = true; c->hint_ge8192 = st.n_ge8192; c->hint_ge2048 = st.n_ge2048; c->hint_ge16384 = st.n_ge16384; }
     if (st.overflow == 0) { c->hint_pairs = st.n_pairs; c->hint_maxlen = st.max_tile_len; c->hint_large = st.n_large; c->hint_window = st.n_window; }
     s.used = false;
-}
-
-std::mutex g_ledger_mu;
-std::unordered_map<void*, std::pair<splat_ctx*, size_t>> g_ledger;
-void ledger_add(splat_ctx* c, void* p, size_t bytes) {
-    std::lock_guard<std::mutex> g(g_ledger_mu);
-    g_ledger[p] = {c, bytes};
-    c->dev_bytes += bytes;
-    c->dev_bytes_peak = std::max(c->dev_bytes_peak, c->dev_bytes);
-}
-void ledger_del(void* p) {
-    std::lock_guard<std::mutex> g(g_ledger_mu);
-    auto it = g_ledger.find(p);
-    if (it == g_ledger.end()) return;
-    it->second.first->dev_bytes -= it->second.second;
-    g_ledger.erase(it);
 }
 
 // Page-locked host ranges this library made (splat_host_alloc / splat_host_register): start -> bytes.  The zero-copy frame
@@ -1257,15 +943,6 @@ void fill_stats(splat_ctx* c, splat_stats* st) {
     st->ms_total = t[0] + t[1] + t[2] + t[3] + t[4];
 }
 
-void free_scene(splat_ctx* c) {
-    dfree(c->planes); dfree(c->orig); dfree(c->bounds);
-    dfree(c->inv); c->upd_bad = nullptr; c->upd_dirty = nullptr;
-    for (Slot& s : c->slots) { dfree(s.recs); dfree(s.depth); dfree(s.rect); dfree(s.vislist); dfree(s.blockinfo); dfree(s.large_list); dfree(s.large_count); s.used = false; }
-    c->n = 0;
-    c->h_orig.clear();
-    c->last_slot = -1;
-}
-
 }  // namespace
 
 namespace {
@@ -1601,47 +1278,37 @@ int splat_set_stream(splat_ctx* c, void* stream) {
 
 }  // extern "C"
 
-namespace {
-// The two scene uploads (host buffers, device buffers) share everything but how the order, the bounds and the planes get
-// their values.  upload_begin: the frames of the scene being replaced end, the old scene goes.
-int upload_begin(splat_ctx* c) {
+// ---- The scheduler's side of the seam to splat_scene.hip (splat_context.h)
+namespace splat {
+// The scene is being replaced: its frames end, and nothing of them is left to redo or to report.
+int end_frames_for_upload(splat_ctx* c) {
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     (void)finish_frame(c);          // (frames of the scene being replaced: nothing left to redo)
     c->deferred_drop = false; c->frames_drop_reported = c->frames_dropped;
-    int rc = sync_all(c);
+    return sync_all(c);
+}
+// The scene is being edited in place: the frames in flight end as above -- they show the scene as it was -- but a frame found
+// skipped stays pending for the next splat_sync, as for every call that quiesces on its way to something else.
+int end_frames_for_edit(splat_ctx* c) {
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    int rc = finish_quiet(c);
     if (rc != SPLAT_OK) return rc;
-    free_scene(c);
-    return SPLAT_OK;
+    return sync_all(c);
 }
-// ... the buffers that live as long as the scene (the bounds apart: the host path makes them once it has their values)
-hipError_t alloc_scene(splat_ctx* c, uint64_t n) {
-    hipError_t e;
-#define AS_TRY(expr) if ((e = (expr)) != hipSuccess) return e
-    AS_TRY(dmalloc(c, &c->planes, sizeof(float4) * SCENE_PLANES * n));
-    AS_TRY(dmalloc(c, &c->orig, sizeof(unsigned int) * n));
-    for (Slot& s : c->slots) {
-        AS_TRY(dmalloc(c, &s.recs, sizeof(Rec) * n));
-        AS_TRY(dmalloc(c, &s.blockinfo, sizeof(unsigned int) * ((n + 255) / 256)));
-        AS_TRY(hipMemsetAsync(s.blockinfo, 0, sizeof(unsigned int) * ((n + 255) / 256), c->stream));
-        if (c->large_tiles >= 0) {          // (SPLAT_LARGE_TILES < 0: no list, K1's blocks expand their close-ups themselves)
-            AS_TRY(dmalloc(c, &s.large_list, sizeof(uint4) * n));
-            AS_TRY(dmalloc(c, &s.large_count, sizeof(unsigned int) * 4));
-            AS_TRY(hipMemsetAsync(s.large_count, 0, sizeof(unsigned int) * 4, c->stream));
-        }
-    }
-#undef AS_TRY
-    return hipSuccess;
+// Other values under every tile: what the region layouts, the sort launch sizes, the walks of the old ones (near selection,
+// start hints) and the frame policy remember says nothing any more.
+void scene_edited(splat_ctx* c) {
+    for (Slot& sl : c->slots) sl.layout_valid = false;
+    c->sort_hint = false;
+    if (c->need_hint && c->m_alloc) (void)fill_now(c->need_hint, 0, hint_table(c).bytes());
+    reset_policy(c);
 }
-// ... and what follows the packing: the context's per-scene state starts over, the per-tile arrays and key buffers exist
-void upload_finish(splat_ctx* c, uint64_t n) {
+// Another scene altogether: the context's per-scene state starts over, the per-tile arrays and key buffers exist.
+void scene_installed(splat_ctx* c, uint64_t n) {
     c->n = n;
     c->region_mult = 0;
     c->bucket_failed = false;              // key storage is sized at the first frame (prepare_binning)
-    for (Slot& sl : c->slots) sl.layout_valid = false;
-    c->sort_hint = false;
-    // another scene under every tile: what the walks of the old one needed says nothing (near selection, start hints)
-    if (c->need_hint && c->m_alloc) (void)fill_now(c->need_hint, 0, hint_table(c).bytes());
-    reset_policy(c);
+    scene_edited(c);
     // The per-tile arrays (a few hundred KB per frame slot at 4K) exist before the first frame as well: fifty small allocations
     // and six synchronous fills were a third of its call.  A larger target than 3840 x 2160 makes them again, as always.
     if (c->m_alloc == 0 && ensure_bins(c, 240u * 135u) != SPLAT_OK) (void)hipGetLastError();
@@ -1653,365 +1320,9 @@ void upload_finish(splat_ctx* c, uint64_t n) {
         if ((want + want2) * 8ull * (uint64_t)slots_in_use(c) <= c->bucket_bytes && ensure_keys(c, want, want2) != SPLAT_OK) (void)hipGetLastError();
     }
 }
-// The host copy of the scene's order (the debug getters translate slots with it): the host upload leaves it behind, a
-// device upload does not -- it is fetched when first asked for.
-int ensure_h_orig(splat_ctx* c) {
-    if (c->h_orig.size() == c->n) return SPLAT_OK;
-    std::vector<unsigned int> h(c->n);
-    if (c->n) HIP_TRY(c, hipMemcpy(h.data(), c->orig, sizeof(unsigned int) * c->n, hipMemcpyDeviceToHost));
-    c->h_orig.swap(h);
-    return SPLAT_OK;
-}
-// Work the caller enqueued on `producer` comes first: the context's stream waits for an event recorded there.
-hipError_t follow_producer(splat_ctx* c, void* producer) {
-    if (!producer) return hipSuccess;          // (the caller has synchronised)
-    hipEvent_t ev = nullptr;
-    hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-    if (e != hipSuccess) return e;
-    e = hipEventRecord(ev, (hipStream_t)producer);
-    if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, ev, 0);
-    (void)hipEventDestroy(ev);                 // (released once the wait has been satisfied)
-    return e;
-}
-}  // namespace
+}  // namespace splat
 
 extern "C" {
-
-// the two uploads' HIP calls: a failure releases the upload's temporaries (`cleanup`) and reports the call (`e`: a local)
-#define UP_TRY(expr)                                                            \
-    if ((e = (expr)) != hipSuccess) {                                            \
-        cleanup();                                                               \
-        return fail(c, SPLAT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e)); \
-    }
-
-int splat_upload_scene(splat_ctx* c, uint64_t n, const float* pos4, const float* cov3d, const float* opacity,
-                       const float* sh) {
-    if (!c) return SPLAT_ERR_INVALID;
-    if (n && (!pos4 || !cov3d || !opacity || !sh)) return fail(c, SPLAT_ERR_INVALID, "NULL scene pointer");
-    if (n >= 0xFFFFFFFFull) return fail(c, SPLAT_ERR_INVALID, "too many Gaussians (index is 32-bit)");
-    int rc = upload_begin(c);
-    if (rc != SPLAT_OK) return rc;
-    if (n == 0) return SPLAT_OK;
-    morton_order(n, pos4, c->h_orig);
-    float *d_pos = nullptr, *d_cov = nullptr, *d_op = nullptr, *d_sh = nullptr;
-    auto cleanup = [&] { dfree(d_pos); dfree(d_cov); dfree(d_op); dfree(d_sh); };
-    hipError_t e;
-    UP_TRY(alloc_scene(c, n));
-    UP_TRY(hipMemcpyAsync(c->orig, c->h_orig.data(), sizeof(unsigned int) * n, hipMemcpyHostToDevice, c->stream));
-    std::vector<BlockBounds> hb;
-    block_bounds(n, pos4, cov3d, c->h_orig, hb);
-    UP_TRY(dmalloc(c, &c->bounds, sizeof(BlockBounds) * hb.size()));
-    UP_TRY(hipMemcpyAsync(c->bounds, hb.data(), sizeof(BlockBounds) * hb.size(), hipMemcpyHostToDevice, c->stream));
-    UP_TRY(dmalloc(c, &d_pos, sizeof(float) * 4 * n));
-    UP_TRY(dmalloc(c, &d_cov, sizeof(float) * 9 * n));
-    UP_TRY(dmalloc(c, &d_op, sizeof(float) * n));
-    UP_TRY(dmalloc(c, &d_sh, sizeof(float) * 48 * n));
-    UP_TRY(hipMemcpyAsync(d_pos, pos4, sizeof(float) * 4 * n, hipMemcpyHostToDevice, c->stream));
-    UP_TRY(hipMemcpyAsync(d_cov, cov3d, sizeof(float) * 9 * n, hipMemcpyHostToDevice, c->stream));
-    UP_TRY(hipMemcpyAsync(d_op, opacity, sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
-    UP_TRY(hipMemcpyAsync(d_sh, sh, sizeof(float) * 48 * n, hipMemcpyHostToDevice, c->stream));
-    launch_pack_scene(c->stream, n, d_pos, d_cov, d_op, d_sh, c->orig, c->planes);
-    UP_TRY(hipGetLastError());
-    UP_TRY(hipStreamSynchronize(c->stream));
-    cleanup();
-    upload_finish(c, n);
-    return SPLAT_OK;
-}
-
-int splat_upload_scene_device(splat_ctx* c, uint64_t n, const void* d_pos4, const void* d_cov3d, const void* d_opacity,
-                              const void* d_sh, void* producer_stream) {
-    if (!c) return SPLAT_ERR_INVALID;
-    if (n && (!d_pos4 || !d_cov3d || !d_opacity || !d_sh)) return fail(c, SPLAT_ERR_INVALID, "NULL scene pointer");
-    if (n >= 0xFFFFFFFFull) return fail(c, SPLAT_ERR_INVALID, "too many Gaussians (index is 32-bit)");
-    int rc = upload_begin(c);
-    if (rc != SPLAT_OK) return rc;
-    if (n == 0) return SPLAT_OK;
-    const float *pos4 = (const float*)d_pos4, *cov3d = (const float*)d_cov3d;
-    // the sort's ping-pong arrays (16 B per Gaussian) and its scan tables: all that exists beside the scene itself
-    uint32_t* d_sort = nullptr; unsigned char* d_small = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    auto cleanup = [&] { dfree(d_sort); dfree(d_small); for (hipEvent_t& x : ev) if (x) { (void)hipEventDestroy(x); x = nullptr; } };
-    hipError_t e;
-    UP_TRY(alloc_scene(c, n));
-    UP_TRY(dmalloc(c, &c->bounds, sizeof(BlockBounds) * ((n + 255) / 256)));
-    UP_TRY(dmalloc(c, &d_sort, sizeof(uint32_t) * 4 * n));
-    UP_TRY(dmalloc(c, &d_small, scene_order_small_bytes(n)));
-    UP_TRY(hipEventCreate(&ev[0]));
-    UP_TRY(hipEventCreate(&ev[1]));
-    UP_TRY(follow_producer(c, producer_stream));
-    launch_scene_order(c->stream, n, pos4, d_sort, d_small, c->orig, ev[0], ev[1]);
-    launch_block_bounds(c->stream, n, pos4, cov3d, c->orig, c->bounds);
-    launch_pack_scene(c->stream, n, pos4, cov3d, (const float*)d_opacity, (const float*)d_sh, c->orig, c->planes);
-    UP_TRY(hipGetLastError());
-    UP_TRY(hipStreamSynchronize(c->stream));
-#undef UP_TRY
-    c->upload_sort_ms = 0.0f;
-    (void)hipEventElapsedTime(&c->upload_sort_ms, ev[0], ev[1]);
-    cleanup();
-    upload_finish(c, n);
-    return SPLAT_OK;
-}
-
-// (debug, not part of the ABI)  Device time of the sort inside the most recent splat_upload_scene_device, in milliseconds.
-int splat_debug_upload_sort_ms(splat_ctx* c, double* ms) {
-    if (!c || !ms) return SPLAT_ERR_INVALID;
-    *ms = c->upload_sort_ms;
-    return SPLAT_OK;
-}
-
-}  // extern "C"
-
-namespace {
-// The two in-place edits (whole fields, by index) share everything but the repack and which blocks get new bounds.
-constexpr uint32_t FIELDS_ALL = SPLAT_FIELD_POS | SPLAT_FIELD_COV3D | SPLAT_FIELD_OPACITY | SPLAT_FIELD_SH;
-// what both refuse before they touch HIP (rows: n or k); nullptr: nothing
-const char* update_refusal(uint64_t rows, uint32_t fields, const void* pos4, const void* cov3d, const void* opacity, const void* sh) {
-    if (fields & ~FIELDS_ALL) return "unknown bits in fields";
-    if (rows && (((fields & SPLAT_FIELD_POS) && !pos4) || ((fields & SPLAT_FIELD_COV3D) && !cov3d) ||
-                 ((fields & SPLAT_FIELD_OPACITY) && !opacity) || ((fields & SPLAT_FIELD_SH) && !sh)))
-        return "NULL pointer for a named field";
-    return nullptr;
-}
-// update_begin: the frames in flight end as upload_begin ends them -- they show the scene as it was -- but the scene stays.
-// A frame found skipped stays pending for the next splat_sync, as for every call that quiesces on its way to something else.
-int update_begin(splat_ctx* c) {
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    int rc = finish_quiet(c);
-    if (rc != SPLAT_OK) return rc;
-    return sync_all(c);
-}
-// ... and update_finish: the per-scene state upload_finish resets, and nothing else -- other values under every tile
-void update_finish(splat_ctx* c) {
-    for (Slot& sl : c->slots) sl.layout_valid = false;
-    c->sort_hint = false;
-    if (c->need_hint && c->m_alloc) (void)fill_now(c->need_hint, 0, hint_table(c).bytes());
-    reset_policy(c);
-}
-// the inverse of the scene's order, the index check's counter and the dirty bytes: made by the first indexed edit of a scene
-hipError_t ensure_inverse(splat_ctx* c) {
-    if (c->inv) return hipSuccess;
-    const uint64_t n = c->n, nb = (n + 255) / 256;
-    hipError_t e = dmalloc(c, &c->inv, sizeof(unsigned int) * n + 16 + nb);
-    if (e != hipSuccess) return e;
-    c->upd_bad = c->inv + n;
-    c->upd_dirty = (unsigned char*)(c->inv + n) + 16;
-    if ((e = hipMemsetAsync(c->upd_bad, 0, 16 + nb, c->stream)) != hipSuccess) { dfree(c->inv); c->upd_bad = nullptr; c->upd_dirty = nullptr; return e; }
-    launch_inverse_order(c->stream, n, c->orig, c->inv);
-    return hipGetLastError();
-}
-}  // namespace
-
-extern "C" {
-
-#define UPD_TRY(expr)                                                           \
-    if ((e = (expr)) != hipSuccess)                                              \
-        return fail(c, SPLAT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e))
-
-int splat_update_scene_device(splat_ctx* c, uint64_t n, uint32_t fields, const void* d_pos4, const void* d_cov3d,
-                              const void* d_opacity, const void* d_sh, void* producer_stream) {
-    if (!c) return fail(c, SPLAT_ERR_INVALID, "NULL context");
-    if (const char* why = update_refusal(n, fields, d_pos4, d_cov3d, d_opacity, d_sh)) return fail(c, SPLAT_ERR_INVALID, why);
-    if (c->n == 0) return fail(c, SPLAT_ERR_NO_SCENE, "no resident scene to update");
-    if (n != c->n) return fail(c, SPLAT_ERR_INVALID, "n is not the resident scene's (changing n is an upload)");
-    if (fields == 0) return SPLAT_OK;
-    int rc = update_begin(c);
-    if (rc != SPLAT_OK) return rc;
-    hipError_t e;
-    UPD_TRY(follow_producer(c, producer_stream));
-    launch_repack_scene(c->stream, n, fields, (const float*)d_pos4, (const float*)d_cov3d, (const float*)d_opacity, (const float*)d_sh,
-                        c->orig, c->planes);
-    if (fields & (SPLAT_FIELD_POS | SPLAT_FIELD_COV3D)) launch_plane_bounds(c->stream, n, c->planes, nullptr, c->bounds);
-    UPD_TRY(hipGetLastError());
-    UPD_TRY(hipStreamSynchronize(c->stream));
-    update_finish(c);
-    return SPLAT_OK;
-}
-
-int splat_update_gaussians_device(splat_ctx* c, uint64_t k, const void* d_index, uint32_t fields, const void* d_pos4,
-                                  const void* d_cov3d, const void* d_opacity, const void* d_sh, void* producer_stream) {
-    if (!c) return fail(c, SPLAT_ERR_INVALID, "NULL context");
-    if (const char* why = update_refusal(k, fields, d_pos4, d_cov3d, d_opacity, d_sh)) return fail(c, SPLAT_ERR_INVALID, why);
-    if (k && !d_index) return fail(c, SPLAT_ERR_INVALID, "NULL index");
-    if (c->n == 0) return fail(c, SPLAT_ERR_NO_SCENE, "no resident scene to update");
-    if (k > c->n) return fail(c, SPLAT_ERR_INVALID, "more indices than Gaussians: they cannot be distinct");
-    if (fields == 0 || k == 0) return SPLAT_OK;
-    int rc = update_begin(c);
-    if (rc != SPLAT_OK) return rc;
-    const uint64_t n = c->n;
-    const unsigned int* index = (const unsigned int*)d_index;
-    hipError_t e;
-    UPD_TRY(ensure_inverse(c));
-    UPD_TRY(follow_producer(c, producer_stream));
-    // the indices first: the count of those that name no Gaussian comes back before anything is written
-    unsigned int bad = 0;
-    UPD_TRY(hipMemsetAsync(c->upd_bad, 0, sizeof(unsigned int), c->stream));
-    launch_index_check(c->stream, k, n, index, c->upd_bad);
-    UPD_TRY(hipGetLastError());
-    UPD_TRY(hipMemcpyAsync(&bad, c->upd_bad, sizeof bad, hipMemcpyDeviceToHost, c->stream));
-    UPD_TRY(hipStreamSynchronize(c->stream));
-    if (bad) return fail(c, SPLAT_ERR_INVALID, "an index is not below n; nothing was applied");
-    const bool rebound = (fields & (SPLAT_FIELD_POS | SPLAT_FIELD_COV3D)) != 0;
-    launch_repack_indexed(c->stream, n, k, index, fields, (const float*)d_pos4, (const float*)d_cov3d, (const float*)d_opacity,
-                          (const float*)d_sh, c->inv, c->planes, rebound ? c->upd_dirty : nullptr);
-    if (rebound) launch_plane_bounds(c->stream, n, c->planes, c->upd_dirty, c->bounds);
-    UPD_TRY(hipGetLastError());
-    UPD_TRY(hipStreamSynchronize(c->stream));
-    update_finish(c);
-    return SPLAT_OK;
-}
-#undef UPD_TRY
-
-}  // extern "C"
-
-namespace {
-// what both PLY entry points refuse before they touch HIP; msg: why
-bool ply_layout_ok(const splat_ply_layout* lay, const char** msg) {
-    if (!lay) { *msg = "NULL layout"; return false; }
-    if (lay->stride == 0) { *msg = "PLY stride is 0"; return false; }
-    for (int k = 0; k < SPLAT_PLY_SLOTS; ++k) {
-        if (lay->offset[k] < -1) { *msg = "PLY property offset below -1"; return false; }
-        if (lay->offset[k] >= 0 && (uint64_t)lay->offset[k] + 4u > lay->stride) { *msg = "PLY property reaches beyond its row"; return false; }
-    }
-    if (lay->n >= 0xFFFFFFFFull) { *msg = "too many Gaussians (index is 32-bit)"; return false; }
-    return true;
-}
-// decode + recentre on the context's stream, behind `producer`, waited for; the mean's three floats are the chain's only
-// temporary.
-hipError_t ply_decode_now(splat_ctx* c, const splat_ply_layout& lay, const void* d_rows, float* pos4, float* scales3,
-                          float* opacity, float* rot4, float* sh, void* producer) {
-    float* d_mean = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    auto cleanup = [&] { dfree(d_mean); for (hipEvent_t& x : ev) if (x) { (void)hipEventDestroy(x); x = nullptr; } };
-    hipError_t e;
-#define PLY_TRY(expr) if ((e = (expr)) != hipSuccess) { cleanup(); return e; }
-    PLY_TRY(dmalloc(c, &d_mean, sizeof(float) * 4));
-    for (hipEvent_t& x : ev) PLY_TRY(hipEventCreate(&x));
-    PLY_TRY(follow_producer(c, producer));
-    launch_ply_decode(c->stream, lay, d_rows, pos4, scales3, opacity, rot4, sh, d_mean, ev);
-    PLY_TRY(hipGetLastError());
-    PLY_TRY(hipStreamSynchronize(c->stream));
-#undef PLY_TRY
-    for (int k = 0; k < 3; ++k) { c->ply_ms[k] = 0.0f; (void)hipEventElapsedTime(&c->ply_ms[k], ev[k], ev[k + 1]); }
-    cleanup();
-    return hipSuccess;
-}
-}  // namespace
-
-extern "C" {
-
-int splat_decode_ply_device(splat_ctx* c, const splat_ply_layout* lay, const void* d_rows, void* d_pos4, void* d_scales3,
-                            void* d_opacity, void* d_rot4, void* d_sh, void* producer_stream) {
-    // (the arguments are judged before the context is looked at, and before any HIP call: without a context the reason is
-    // what splat_last_error(NULL) reports)
-    const char* why = nullptr;
-    if (!ply_layout_ok(lay, &why)) return fail(c, SPLAT_ERR_INVALID, why);
-    if (!c) return fail(c, SPLAT_ERR_INVALID, "NULL context");
-    if (lay->n == 0) return SPLAT_OK;
-    if (!d_rows || !d_pos4 || !d_scales3 || !d_opacity || !d_rot4 || !d_sh) return fail(c, SPLAT_ERR_INVALID, "NULL pointer");
-    if (((uintptr_t)d_pos4 & 15u) || (((uintptr_t)d_scales3 | (uintptr_t)d_opacity | (uintptr_t)d_rot4 | (uintptr_t)d_sh) & 3u))
-        return fail(c, SPLAT_ERR_INVALID, "output buffer misaligned (pos4: 16 bytes, the others: 4)");
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    hipError_t e = ply_decode_now(c, *lay, d_rows, (float*)d_pos4, (float*)d_scales3, (float*)d_opacity, (float*)d_rot4, (float*)d_sh, producer_stream);
-    if (e != hipSuccess) return fail(c, SPLAT_ERR_HIP, std::string("splat_decode_ply_device: ") + hipGetErrorString(e));
-    return SPLAT_OK;
-}
-
-int splat_upload_ply_device(splat_ctx* c, const splat_ply_layout* lay, const void* d_rows, int32_t compute_cov3d, void* producer_stream) {
-    const char* why = nullptr;
-    if (!ply_layout_ok(lay, &why)) return fail(c, SPLAT_ERR_INVALID, why);
-    if (!c) return fail(c, SPLAT_ERR_INVALID, "NULL context");
-    if (lay->n == 0) return splat_upload_scene_device(c, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
-    if (!d_rows) return fail(c, SPLAT_ERR_INVALID, "NULL pointer");
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    const uint64_t n = lay->n;
-    float *d_pos = nullptr, *d_sc = nullptr, *d_op = nullptr, *d_rot = nullptr, *d_sh = nullptr, *d_cov = nullptr;
-    auto cleanup = [&] { dfree(d_pos); dfree(d_sc); dfree(d_op); dfree(d_rot); dfree(d_sh); dfree(d_cov); };
-    hipError_t e;
-#define PLY_TRY(expr)                                                                                      \
-    if ((e = (expr)) != hipSuccess) {                                                                       \
-        cleanup();                                                                                          \
-        return fail(c, SPLAT_ERR_HIP, std::string("splat_upload_ply_device: " #expr ": ") + hipGetErrorString(e)); \
-    }
-    PLY_TRY(dmalloc(c, &d_pos, sizeof(float) * 4 * n));
-    PLY_TRY(dmalloc(c, &d_sc, sizeof(float) * 3 * n));
-    PLY_TRY(dmalloc(c, &d_op, sizeof(float) * n));
-    PLY_TRY(dmalloc(c, &d_rot, sizeof(float) * 4 * n));
-    PLY_TRY(dmalloc(c, &d_sh, sizeof(float) * 48 * n));
-    PLY_TRY(dmalloc(c, &d_cov, sizeof(float) * 9 * n));
-    // cov3d first, on the same stream: K0 behind the decode (GaussianList::from_vec), or zeros (Gaussian::new)
-    PLY_TRY(ply_decode_now(c, *lay, d_rows, d_pos, d_sc, d_op, d_rot, d_sh, producer_stream));
-    if (compute_cov3d) {
-        launch_cov3d(c->stream, n, d_sc, d_rot, d_cov);
-        PLY_TRY(hipGetLastError());
-    } else {
-        PLY_TRY(hipMemsetAsync(d_cov, 0, sizeof(float) * 9 * n, c->stream));
-    }
-    PLY_TRY(hipStreamSynchronize(c->stream));
-#undef PLY_TRY
-    dfree(d_sc); dfree(d_rot);
-    const int rc = splat_upload_scene_device(c, n, d_pos, d_cov, d_op, d_sh, nullptr);
-    cleanup();
-    return rc;
-}
-
-// (debug, not part of the ABI)  Device time of the decode, the sequential sum and the subtraction inside the most recent
-// splat_decode_ply_device / splat_upload_ply_device, in milliseconds.
-int splat_debug_ply_ms(splat_ctx* c, double ms[3]) {
-    if (!c || !ms) return SPLAT_ERR_INVALID;
-    for (int k = 0; k < 3; ++k) ms[k] = c->ply_ms[k];
-    return SPLAT_OK;
-}
-
-int splat_get_scene_layout(splat_ctx* c, uint32_t* orig_out, uint64_t n, float* bounds_out, uint64_t n_blocks) {
-    if (!c) return SPLAT_ERR_INVALID;
-    if (n != c->n || n_blocks != (c->n + 255) / 256) return fail(c, SPLAT_ERR_INVALID, "scene layout size mismatch");
-    if (n == 0) return SPLAT_OK;
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    static_assert(sizeof(BlockBounds) == 8 * sizeof(float), "bounds_out is 8 floats per block");
-    if (orig_out) HIP_TRY(c, hipMemcpy(orig_out, c->orig, sizeof(unsigned int) * n, hipMemcpyDeviceToHost));
-    if (bounds_out) HIP_TRY(c, hipMemcpy(bounds_out, c->bounds, sizeof(BlockBounds) * n_blocks, hipMemcpyDeviceToHost));
-    return SPLAT_OK;
-}
-
-int splat_compute_cov3d(splat_ctx* c, uint64_t n, const float* scales3, const float* rot4, float* cov3d_out) {
-    if (!c) return SPLAT_ERR_INVALID;
-    if (n == 0) return SPLAT_OK;
-    if (!scales3 || !rot4 || !cov3d_out) return fail(c, SPLAT_ERR_INVALID, "NULL pointer");
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    float *d_s = nullptr, *d_r = nullptr, *d_o = nullptr;
-    hipError_t e = hipSuccess;
-    int rc = SPLAT_OK;
-    do {
-        if ((e = dmalloc(c, &d_s, sizeof(float) * 3 * n)) != hipSuccess) break;
-        if ((e = dmalloc(c, &d_r, sizeof(float) * 4 * n)) != hipSuccess) break;
-        if ((e = dmalloc(c, &d_o, sizeof(float) * 9 * n)) != hipSuccess) break;
-        if ((e = hipMemcpyAsync(d_s, scales3, sizeof(float) * 3 * n, hipMemcpyHostToDevice, c->stream)) != hipSuccess) break;
-        if ((e = hipMemcpyAsync(d_r, rot4, sizeof(float) * 4 * n, hipMemcpyHostToDevice, c->stream)) != hipSuccess) break;
-        launch_cov3d(c->stream, n, d_s, d_r, d_o);
-        if ((e = hipGetLastError()) != hipSuccess) break;
-        if ((e = hipMemcpyAsync(cov3d_out, d_o, sizeof(float) * 9 * n, hipMemcpyDeviceToHost, c->stream)) != hipSuccess) break;
-        e = hipStreamSynchronize(c->stream);
-    } while (0);
-    if (e != hipSuccess) rc = fail(c, SPLAT_ERR_HIP, std::string("splat_compute_cov3d: ") + hipGetErrorString(e));
-    dfree(d_s); dfree(d_r); dfree(d_o);
-    return rc;
-}
-
-int splat_compute_cov3d_device(splat_ctx* c, uint64_t n, const void* d_scales3, const void* d_rot4, void* d_cov3d_out,
-                               void* producer_stream) {
-    if (!c) return SPLAT_ERR_INVALID;
-    if (n == 0) return SPLAT_OK;
-    if (!d_scales3 || !d_rot4 || !d_cov3d_out) return fail(c, SPLAT_ERR_INVALID, "NULL pointer");
-    HIP_TRY(c, hipSetDevice(c->cfg.device));
-    hipError_t e = follow_producer(c, producer_stream);
-    if (e == hipSuccess) {
-        launch_cov3d(c->stream, n, (const float*)d_scales3, (const float*)d_rot4, (float*)d_cov3d_out);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return fail(c, SPLAT_ERR_HIP, std::string("splat_compute_cov3d_device: ") + hipGetErrorString(e));
-    return SPLAT_OK;
-}
 
 int splat_set_slab(splat_ctx* c, int32_t tile_row0, int32_t tile_row1) {
     if (!c) return SPLAT_ERR_INVALID;

@@ -1,4 +1,5 @@
-// splat_internal.h -- shared between splat_api.hip (host) and splat_kernels.hip (gfx950 kernels).
+// splat_internal.h -- shared between the host files (splat_api.hip, splat_scene.hip) and the kernel files (splat_kernels.hip,
+// splat_ply.hip, splat_update.hip).
 #ifndef SPLAT_INTERNAL_H
 #define SPLAT_INTERNAL_H
 #include <hip/hip_runtime.h>
@@ -145,12 +146,12 @@ void launch_pack_scene(hipStream_t s, uint64_t n, const float* pos4, const float
                        const float* sh, const unsigned int* perm, float4* planes);
 void launch_cov3d(hipStream_t s, uint64_t n, const float* scales3, const float* rot4, float* cov3d);
 // The scene's order on the device (splat_upload_scene_device): orig[j] = the Gaussian stored in slot j, as morton_order of
-// splat_api.hip orders them.  pingpong: 4 n words (the sort's two key and two index arrays); small:
+// splat_scene.hip orders them.  pingpong: 4 n words (the sort's two key and two index arrays); small:
 // scene_order_small_bytes(n) bytes (scan tables, partial boxes).  The two events, when given, are recorded around the sort.
 size_t scene_order_small_bytes(uint64_t n);
 void launch_scene_order(hipStream_t s, uint64_t n, const float* pos4, uint32_t* pingpong, void* small, unsigned int* orig,
                         hipEvent_t sort_begin = nullptr, hipEvent_t sort_end = nullptr);
-// ... and the bounds of its K1 blocks, as block_bounds of splat_api.hip computes them
+// ... and the bounds of its K1 blocks, as block_bounds of splat_scene.hip computes them
 void launch_block_bounds(hipStream_t s, uint64_t n, const float* pos4, const float* cov3d, const unsigned int* orig, BlockBounds* bounds);
 
 // PLY vertex rows -> the five SoA buffers, activated and recentred as load_from_ply does (splat_ply.hip): decode, the
@@ -296,7 +297,8 @@ struct CompositeArgs {
 void launch_composite(const CompositeArgs& a);
 hipError_t init_device_kernels();   // per-device kernel attributes; call with the device current
 
-// ---- splat_multi.hip: the multi-GPU layer's hooks into a context (splat_ctx itself stays private to splat_api.hip)
+// ---- splat_multi.hip: the multi-GPU layer's hooks into a context (splat_ctx itself stays private to the host files that
+// include splat_context.h: splat_api.hip, splat_scene.hip)
 struct CommState;                              // RCCL communicator + partition of one context
 CommState** ctx_comm_slot(splat_ctx* c);
 hipStream_t ctx_stream(splat_ctx* c);

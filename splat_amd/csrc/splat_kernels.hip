@@ -164,7 +164,7 @@ __global__ __launch_bounds__(256) void cov3d_kernel(uint64_t n, const float* __r
 
 // ---------------------------------------------------------------------------
 // Scene order and block bounds on the device (splat_upload_scene_device).  morton_order and block_bounds of
-// splat_api.hip are the specification: the same f32 arithmetic, the same order among equal codes, the same bits in the
+// splat_scene.hip are the specification: the same f32 arithmetic, the same order among equal codes, the same bits in the
 // bounds -- a frame after a device upload is the frame after a host upload of the same data.
 //   scene_box_kernel / scene_box_final_kernel   per-axis min / max of the finite coordinates, then lo and 1023 / (hi - lo)
 //   morton_code_kernel                          the 30-bit code of every Gaussian
@@ -374,7 +374,7 @@ __global__ __launch_bounds__(256) void radix_scatter_kernel(uint64_t n, const ui
     }
 }
 
-// Bounds of K1 block blockIdx.x (block_bounds of splat_api.hip): thread t holds slot 256 b + t.  The reductions keep the
+// Bounds of K1 block blockIdx.x (block_bounds of splat_scene.hip): thread t holds slot 256 b + t.  The reductions keep the
 // host loop's order, so the earlier of two equal coordinates is the one that stays.
 __global__ __launch_bounds__(256) void block_bounds_kernel(uint64_t n, const float* __restrict__ pos4, const float* __restrict__ cov3d,
                                                            const unsigned int* __restrict__ orig, BlockBounds* __restrict__ out) {

@@ -1,0 +1,462 @@
+// splat_scene.hip -- everything that puts values into the resident scene: the uploads (host buffers, device buffers, PLY
+// rows), the in-place edits, K0 (cov3d) and the scene's layout read back.  Host side only, no device code: the kernels are
+// splat_kernels.hip's (order, bounds, packing), splat_ply.hip's and splat_update.hip's.  What the frame scheduler
+// (splat_api.hip) holds per scene is behind the seam of splat_context.h.
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "splat_context.h"
+
+using namespace splat;
+
+namespace {
+
+// helpers that return hipError_t hand a failed call's error on; the entry point's HIP_TRY names the helper and reports it
+#define HIP_RET(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return _e; } while (0)
+
+// The device buffers and events a call needs only while it runs: all of them go with their owner, on every way out.
+struct Temps {
+    explicit Temps(splat_ctx* ctx) : c(ctx) {}
+    Temps(const Temps&) = delete;
+    Temps& operator=(const Temps&) = delete;
+    ~Temps() {
+        for (void*& p : bufs) dfree(p);
+        for (hipEvent_t e : events) (void)hipEventDestroy(e);
+    }
+    template <typename T>
+    hipError_t alloc(T** p, size_t bytes) {
+        hipError_t e = dmalloc(c, p, bytes);
+        if (e == hipSuccess) bufs.push_back((void*)*p);
+        return e;
+    }
+    template <typename T>
+    void release(T*& p) {                      // ahead of the owner: what comes next needs the room
+        bufs.erase(std::remove(bufs.begin(), bufs.end(), (void*)p), bufs.end());
+        dfree(p);
+    }
+    hipError_t event(hipEvent_t* e) {          // (with timing)
+        hipError_t err = hipEventCreate(e);
+        if (err == hipSuccess) events.push_back(*e);
+        return err;
+    }
+    splat_ctx* c;
+    std::vector<void*> bufs;
+    std::vector<hipEvent_t> events;
+};
+
+// A failed upload leaves no scene -- the context is as splat_upload_scene(n = 0) leaves it -- and the failure's message.
+// The one exception: frames that cannot be ended (end_frames_for_upload fails) keep the scene they read, here as in an upload.
+struct SceneGuard {
+    splat_ctx* c;
+    bool frames_ended;         // false: the old scene is still resident and its frames may be in flight (a PLY upload's decode)
+    bool armed = true;         // until the upload has reached scene_installed
+    ~SceneGuard() {
+        if (!armed) return;
+        const std::string why = c->err;
+        if (frames_ended || end_frames_for_upload(c) == SPLAT_OK) free_scene(c);
+        c->err = why;
+    }
+};
+
+// Upload-time ordering: 30-bit Morton code of the position inside the scene's bounding box.
+// order[j] = original index stored in slot j.  Ties keep index order; non-finite positions go first.
+inline uint32_t spread3(uint32_t v) {
+    v &= 0x3ffu;
+    v = (v | (v << 16)) & 0x030000ffu;
+    v = (v | (v << 8)) & 0x0300f00fu;
+    v = (v | (v << 4)) & 0x030c30c3u;
+    v = (v | (v << 2)) & 0x09249249u;
+    return v;
+}
+void morton_order(uint64_t n, const float* pos4, std::vector<unsigned int>& order) {
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (uint64_t i = 0; i < n; ++i)
+        for (int a = 0; a < 3; ++a) {
+            float v = pos4[4 * i + a];
+            if (std::isfinite(v)) { lo[a] = std::min(lo[a], v); hi[a] = std::max(hi[a], v); }
+        }
+    float sc[3];
+    for (int a = 0; a < 3; ++a) sc[a] = (hi[a] > lo[a]) ? 1023.0f / (hi[a] - lo[a]) : 0.0f;
+    std::vector<uint64_t> keyed(n);
+    for (uint64_t i = 0; i < n; ++i) {
+        uint32_t code = 0;
+        for (int a = 0; a < 3; ++a) {
+            float v = pos4[4 * i + a];
+            uint32_t q = std::isfinite(v) ? (uint32_t)std::min(1023.0f, std::max(0.0f, (v - lo[a]) * sc[a])) : 0u;
+            code |= spread3(q) << a;
+        }
+        keyed[i] = ((uint64_t)code << 32) | (uint64_t)i;
+    }
+    std::sort(keyed.begin(), keyed.end());
+    order.resize(n);
+    for (uint64_t j = 0; j < n; ++j) order[j] = (unsigned int)keyed[j];
+}
+
+// Bounds of every K1 block (256 consecutive slots): AABB of the finite centres, largest ||cov3d||_F.
+void block_bounds(uint64_t n, const float* pos4, const float* cov3d, const std::vector<unsigned int>& order,
+                  std::vector<BlockBounds>& out) {
+    const uint64_t nb = (n + 255) / 256;
+    out.resize(nb);
+    for (uint64_t b = 0; b < nb; ++b) {
+        BlockBounds bb;
+        for (int a = 0; a < 3; ++a) { bb.lo[a] = INFINITY; bb.hi[a] = -INFINITY; }
+        bb.fmax = 0.0f; bb.pad = 0.0f;
+        const uint64_t j1 = std::min<uint64_t>(n, (b + 1) * 256);
+        for (uint64_t j = b * 256; j < j1; ++j) {
+            const uint64_t i = order[j];
+            const float* p = pos4 + 4 * i;
+            if (!(std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]))) continue;   // never visible
+            for (int a = 0; a < 3; ++a) { bb.lo[a] = std::min(bb.lo[a], p[a]); bb.hi[a] = std::max(bb.hi[a], p[a]); }
+            double f2 = 0.0;
+            for (int e = 0; e < 9; ++e) f2 += (double)cov3d[9 * i + e] * (double)cov3d[9 * i + e];
+            float f = (float)std::sqrt(f2) * 1.0001f;
+            if (!(f >= 0.0f)) f = INFINITY;                    // NaN: unbounded extent
+            bb.fmax = std::max(bb.fmax, f);
+        }
+        if (!(bb.lo[0] <= bb.hi[0]))                            // no finite centre at all: NaN bounds answer "maybe"
+            for (int a = 0; a < 3; ++a) { bb.lo[a] = NAN; bb.hi[a] = NAN; }
+        out[b] = bb;
+    }
+}
+
+// the buffers that live as long as the scene (the bounds apart: the host path makes them once it has their values)
+hipError_t alloc_scene(splat_ctx* c, uint64_t n) {
+    HIP_RET(dmalloc(c, &c->planes, sizeof(float4) * SCENE_PLANES * n));
+    HIP_RET(dmalloc(c, &c->orig, sizeof(unsigned int) * n));
+    for (Slot& s : c->slots) {
+        HIP_RET(dmalloc(c, &s.recs, sizeof(Rec) * n));
+        HIP_RET(dmalloc(c, &s.blockinfo, sizeof(unsigned int) * ((n + 255) / 256)));
+        HIP_RET(hipMemsetAsync(s.blockinfo, 0, sizeof(unsigned int) * ((n + 255) / 256), c->stream));
+        if (c->large_tiles >= 0) {          // (SPLAT_LARGE_TILES < 0: no list, K1's blocks expand their close-ups themselves)
+            HIP_RET(dmalloc(c, &s.large_list, sizeof(uint4) * n));
+            HIP_RET(dmalloc(c, &s.large_count, sizeof(unsigned int) * 4));
+            HIP_RET(hipMemsetAsync(s.large_count, 0, sizeof(unsigned int) * 4, c->stream));
+        }
+    }
+    return hipSuccess;
+}
+// Work the caller enqueued on `producer` comes first: the context's stream waits for an event recorded there.
+hipError_t follow_producer(splat_ctx* c, void* producer) {
+    if (!producer) return hipSuccess;          // (the caller has synchronised)
+    hipEvent_t ev = nullptr;
+    hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    if (e != hipSuccess) return e;
+    e = hipEventRecord(ev, (hipStream_t)producer);
+    if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, ev, 0);
+    (void)hipEventDestroy(ev);                 // (released once the wait has been satisfied)
+    return e;
+}
+
+// The two in-place edits (whole fields, by index) share everything but the repack and which blocks get new bounds.
+constexpr uint32_t FIELDS_ALL = SPLAT_FIELD_POS | SPLAT_FIELD_COV3D | SPLAT_FIELD_OPACITY | SPLAT_FIELD_SH;
+// what both refuse before they touch HIP (rows: n or k); nullptr: nothing
+const char* update_refusal(uint64_t rows, uint32_t fields, const void* pos4, const void* cov3d, const void* opacity, const void* sh) {
+    if (fields & ~FIELDS_ALL) return "unknown bits in fields";
+    if (rows && (((fields & SPLAT_FIELD_POS) && !pos4) || ((fields & SPLAT_FIELD_COV3D) && !cov3d) ||
+                 ((fields & SPLAT_FIELD_OPACITY) && !opacity) || ((fields & SPLAT_FIELD_SH) && !sh)))
+        return "NULL pointer for a named field";
+    return nullptr;
+}
+// the inverse of the scene's order, the index check's counter and the dirty bytes: made by the first indexed edit of a scene
+hipError_t ensure_inverse(splat_ctx* c) {
+    if (c->inv) return hipSuccess;
+    const uint64_t n = c->n, nb = (n + 255) / 256;
+    HIP_RET(dmalloc(c, &c->inv, sizeof(unsigned int) * n + 16 + nb));
+    c->upd_bad = c->inv + n;
+    c->upd_dirty = (unsigned char*)(c->inv + n) + 16;
+    hipError_t e = hipMemsetAsync(c->upd_bad, 0, 16 + nb, c->stream);
+    if (e != hipSuccess) { dfree(c->inv); c->upd_bad = nullptr; c->upd_dirty = nullptr; return e; }
+    launch_inverse_order(c->stream, n, c->orig, c->inv);
+    return hipGetLastError();
+}
+
+// what both PLY entry points refuse before they touch HIP; msg: why
+bool ply_layout_ok(const splat_ply_layout* lay, const char** msg) {
+    if (!lay) { *msg = "NULL layout"; return false; }
+    if (lay->stride == 0) { *msg = "PLY stride is 0"; return false; }
+    for (int k = 0; k < SPLAT_PLY_SLOTS; ++k) {
+        if (lay->offset[k] < -1) { *msg = "PLY property offset below -1"; return false; }
+        if (lay->offset[k] >= 0 && (uint64_t)lay->offset[k] + 4u > lay->stride) { *msg = "PLY property reaches beyond its row"; return false; }
+    }
+    if (lay->n >= 0xFFFFFFFFull) { *msg = "too many Gaussians (index is 32-bit)"; return false; }
+    return true;
+}
+// decode + recentre on the context's stream, behind `producer`, waited for; the mean's three floats are the chain's only
+// temporary.
+hipError_t ply_decode_now(splat_ctx* c, const splat_ply_layout& lay, const void* d_rows, float* pos4, float* scales3,
+                          float* opacity, float* rot4, float* sh, void* producer) {
+    Temps t(c);
+    float* d_mean = nullptr;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    HIP_RET(t.alloc(&d_mean, sizeof(float) * 4));
+    for (hipEvent_t& x : ev) HIP_RET(t.event(&x));
+    HIP_RET(follow_producer(c, producer));
+    launch_ply_decode(c->stream, lay, d_rows, pos4, scales3, opacity, rot4, sh, d_mean, ev);
+    HIP_RET(hipGetLastError());
+    HIP_RET(hipStreamSynchronize(c->stream));
+    for (int k = 0; k < 3; ++k) { c->ply_ms[k] = 0.0f; (void)hipEventElapsedTime(&c->ply_ms[k], ev[k], ev[k + 1]); }
+    return hipSuccess;
+}
+}  // namespace
+
+namespace splat {
+void free_scene(splat_ctx* c) {
+    dfree(c->planes); dfree(c->orig); dfree(c->bounds);
+    dfree(c->inv); c->upd_bad = nullptr; c->upd_dirty = nullptr;
+    for (Slot& s : c->slots) { dfree(s.recs); dfree(s.depth); dfree(s.rect); dfree(s.vislist); dfree(s.blockinfo); dfree(s.large_list); dfree(s.large_count); s.used = false; }
+    c->n = 0;
+    c->h_orig.clear();
+    c->last_slot = -1;
+}
+// The host copy of the scene's order (the debug getters translate slots with it): the host upload leaves it behind, a
+// device upload does not -- it is fetched when first asked for.
+int ensure_h_orig(splat_ctx* c) {
+    if (c->h_orig.size() == c->n) return SPLAT_OK;
+    std::vector<unsigned int> h(c->n);
+    if (c->n) HIP_TRY(c, hipMemcpy(h.data(), c->orig, sizeof(unsigned int) * c->n, hipMemcpyDeviceToHost));
+    c->h_orig.swap(h);
+    return SPLAT_OK;
+}
+}  // namespace splat
+
+extern "C" {
+
+// The two scene uploads (host buffers, device buffers) share everything but how the order, the bounds and the planes get
+// their values: the frames of the scene being replaced end, the old scene goes, the new one is made and installed.  Their
+// temporaries go before scene_installed makes the key buffers: the upload's peak is the scene's own.
+int splat_upload_scene(splat_ctx* c, uint64_t n, const float* pos4, const float* cov3d, const float* opacity,
+                       const float* sh) {
+    if (!c) return SPLAT_ERR_INVALID;
+    if (n && (!pos4 || !cov3d || !opacity || !sh)) return fail(c, SPLAT_ERR_INVALID, "NULL scene pointer");
+    if (n >= 0xFFFFFFFFull) return fail(c, SPLAT_ERR_INVALID, "too many Gaussians (index is 32-bit)");
+    int rc = end_frames_for_upload(c);
+    if (rc != SPLAT_OK) return rc;
+    free_scene(c);
+    if (n == 0) return SPLAT_OK;
+    SceneGuard guard{c, true};
+    morton_order(n, pos4, c->h_orig);
+    {
+        Temps t(c);
+        float *d_pos = nullptr, *d_cov = nullptr, *d_op = nullptr, *d_sh = nullptr;
+        HIP_TRY(c, alloc_scene(c, n));
+        HIP_TRY(c, hipMemcpyAsync(c->orig, c->h_orig.data(), sizeof(unsigned int) * n, hipMemcpyHostToDevice, c->stream));
+        std::vector<BlockBounds> hb;
+        block_bounds(n, pos4, cov3d, c->h_orig, hb);
+        HIP_TRY(c, dmalloc(c, &c->bounds, sizeof(BlockBounds) * hb.size()));
+        HIP_TRY(c, hipMemcpyAsync(c->bounds, hb.data(), sizeof(BlockBounds) * hb.size(), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, t.alloc(&d_pos, sizeof(float) * 4 * n));
+        HIP_TRY(c, t.alloc(&d_cov, sizeof(float) * 9 * n));
+        HIP_TRY(c, t.alloc(&d_op, sizeof(float) * n));
+        HIP_TRY(c, t.alloc(&d_sh, sizeof(float) * 48 * n));
+        HIP_TRY(c, hipMemcpyAsync(d_pos, pos4, sizeof(float) * 4 * n, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(d_cov, cov3d, sizeof(float) * 9 * n, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(d_op, opacity, sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(d_sh, sh, sizeof(float) * 48 * n, hipMemcpyHostToDevice, c->stream));
+        launch_pack_scene(c->stream, n, d_pos, d_cov, d_op, d_sh, c->orig, c->planes);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    scene_installed(c, n);
+    guard.armed = false;
+    return SPLAT_OK;
+}
+
+int splat_upload_scene_device(splat_ctx* c, uint64_t n, const void* d_pos4, const void* d_cov3d, const void* d_opacity,
+                              const void* d_sh, void* producer_stream) {
+    if (!c) return SPLAT_ERR_INVALID;
+    if (n && (!d_pos4 || !d_cov3d || !d_opacity || !d_sh)) return fail(c, SPLAT_ERR_INVALID, "NULL scene pointer");
+    if (n >= 0xFFFFFFFFull) return fail(c, SPLAT_ERR_INVALID, "too many Gaussians (index is 32-bit)");
+    int rc = end_frames_for_upload(c);
+    if (rc != SPLAT_OK) return rc;
+    free_scene(c);
+    if (n == 0) return SPLAT_OK;
+    SceneGuard guard{c, true};
+    const float *pos4 = (const float*)d_pos4, *cov3d = (const float*)d_cov3d;
+    {
+        // the sort's ping-pong arrays (16 B per Gaussian) and its scan tables: all that exists beside the scene itself
+        Temps t(c);
+        uint32_t* d_sort = nullptr; unsigned char* d_small = nullptr;
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        HIP_TRY(c, alloc_scene(c, n));
+        HIP_TRY(c, dmalloc(c, &c->bounds, sizeof(BlockBounds) * ((n + 255) / 256)));
+        HIP_TRY(c, t.alloc(&d_sort, sizeof(uint32_t) * 4 * n));
+        HIP_TRY(c, t.alloc(&d_small, scene_order_small_bytes(n)));
+        HIP_TRY(c, t.event(&ev[0]));
+        HIP_TRY(c, t.event(&ev[1]));
+        HIP_TRY(c, follow_producer(c, producer_stream));
+        launch_scene_order(c->stream, n, pos4, d_sort, d_small, c->orig, ev[0], ev[1]);
+        launch_block_bounds(c->stream, n, pos4, cov3d, c->orig, c->bounds);
+        launch_pack_scene(c->stream, n, pos4, cov3d, (const float*)d_opacity, (const float*)d_sh, c->orig, c->planes);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        c->upload_sort_ms = 0.0f;
+        (void)hipEventElapsedTime(&c->upload_sort_ms, ev[0], ev[1]);
+    }
+    scene_installed(c, n);
+    guard.armed = false;
+    return SPLAT_OK;
+}
+
+// (debug, not part of the ABI)  Device time of the sort inside the most recent splat_upload_scene_device, in milliseconds.
+int splat_debug_upload_sort_ms(splat_ctx* c, double* ms) {
+    if (!c || !ms) return SPLAT_ERR_INVALID;
+    *ms = c->upload_sort_ms;
+    return SPLAT_OK;
+}
+
+int splat_update_scene_device(splat_ctx* c, uint64_t n, uint32_t fields, const void* d_pos4, const void* d_cov3d,
+                              const void* d_opacity, const void* d_sh, void* producer_stream) {
+    if (!c) return fail(c, SPLAT_ERR_INVALID, "NULL context");
+    if (const char* why = update_refusal(n, fields, d_pos4, d_cov3d, d_opacity, d_sh)) return fail(c, SPLAT_ERR_INVALID, why);
+    if (c->n == 0) return fail(c, SPLAT_ERR_NO_SCENE, "no resident scene to update");
+    if (n != c->n) return fail(c, SPLAT_ERR_INVALID, "n is not the resident scene's (changing n is an upload)");
+    if (fields == 0) return SPLAT_OK;
+    int rc = end_frames_for_edit(c);
+    if (rc != SPLAT_OK) return rc;
+    HIP_TRY(c, follow_producer(c, producer_stream));
+    launch_repack_scene(c->stream, n, fields, (const float*)d_pos4, (const float*)d_cov3d, (const float*)d_opacity, (const float*)d_sh,
+                        c->orig, c->planes);
+    if (fields & (SPLAT_FIELD_POS | SPLAT_FIELD_COV3D)) launch_plane_bounds(c->stream, n, c->planes, nullptr, c->bounds);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    scene_edited(c);
+    return SPLAT_OK;
+}
+
+int splat_update_gaussians_device(splat_ctx* c, uint64_t k, const void* d_index, uint32_t fields, const void* d_pos4,
+                                  const void* d_cov3d, const void* d_opacity, const void* d_sh, void* producer_stream) {
+    if (!c) return fail(c, SPLAT_ERR_INVALID, "NULL context");
+    if (const char* why = update_refusal(k, fields, d_pos4, d_cov3d, d_opacity, d_sh)) return fail(c, SPLAT_ERR_INVALID, why);
+    if (k && !d_index) return fail(c, SPLAT_ERR_INVALID, "NULL index");
+    if (c->n == 0) return fail(c, SPLAT_ERR_NO_SCENE, "no resident scene to update");
+    if (k > c->n) return fail(c, SPLAT_ERR_INVALID, "more indices than Gaussians: they cannot be distinct");
+    if (fields == 0 || k == 0) return SPLAT_OK;
+    int rc = end_frames_for_edit(c);
+    if (rc != SPLAT_OK) return rc;
+    const uint64_t n = c->n;
+    const unsigned int* index = (const unsigned int*)d_index;
+    HIP_TRY(c, ensure_inverse(c));
+    HIP_TRY(c, follow_producer(c, producer_stream));
+    // the indices first: the count of those that name no Gaussian comes back before anything is written
+    unsigned int bad = 0;
+    HIP_TRY(c, hipMemsetAsync(c->upd_bad, 0, sizeof(unsigned int), c->stream));
+    launch_index_check(c->stream, k, n, index, c->upd_bad);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(&bad, c->upd_bad, sizeof bad, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (bad) return fail(c, SPLAT_ERR_INVALID, "an index is not below n; nothing was applied");
+    const bool rebound = (fields & (SPLAT_FIELD_POS | SPLAT_FIELD_COV3D)) != 0;
+    launch_repack_indexed(c->stream, n, k, index, fields, (const float*)d_pos4, (const float*)d_cov3d, (const float*)d_opacity,
+                          (const float*)d_sh, c->inv, c->planes, rebound ? c->upd_dirty : nullptr);
+    if (rebound) launch_plane_bounds(c->stream, n, c->planes, c->upd_dirty, c->bounds);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    scene_edited(c);
+    return SPLAT_OK;
+}
+
+int splat_decode_ply_device(splat_ctx* c, const splat_ply_layout* lay, const void* d_rows, void* d_pos4, void* d_scales3,
+                            void* d_opacity, void* d_rot4, void* d_sh, void* producer_stream) {
+    // (the arguments are judged before the context is looked at, and before any HIP call: without a context the reason is
+    // what splat_last_error(NULL) reports)
+    const char* why = nullptr;
+    if (!ply_layout_ok(lay, &why)) return fail(c, SPLAT_ERR_INVALID, why);
+    if (!c) return fail(c, SPLAT_ERR_INVALID, "NULL context");
+    if (lay->n == 0) return SPLAT_OK;
+    if (!d_rows || !d_pos4 || !d_scales3 || !d_opacity || !d_rot4 || !d_sh) return fail(c, SPLAT_ERR_INVALID, "NULL pointer");
+    if (((uintptr_t)d_pos4 & 15u) || (((uintptr_t)d_scales3 | (uintptr_t)d_opacity | (uintptr_t)d_rot4 | (uintptr_t)d_sh) & 3u))
+        return fail(c, SPLAT_ERR_INVALID, "output buffer misaligned (pos4: 16 bytes, the others: 4)");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, ply_decode_now(c, *lay, d_rows, (float*)d_pos4, (float*)d_scales3, (float*)d_opacity, (float*)d_rot4, (float*)d_sh, producer_stream));
+    return SPLAT_OK;
+}
+
+int splat_upload_ply_device(splat_ctx* c, const splat_ply_layout* lay, const void* d_rows, int32_t compute_cov3d, void* producer_stream) {
+    const char* why = nullptr;
+    if (!ply_layout_ok(lay, &why)) return fail(c, SPLAT_ERR_INVALID, why);
+    if (!c) return fail(c, SPLAT_ERR_INVALID, "NULL context");
+    if (lay->n == 0) return splat_upload_scene_device(c, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
+    if (!d_rows) return fail(c, SPLAT_ERR_INVALID, "NULL pointer");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    const uint64_t n = lay->n;
+    // The old scene stays resident under the decode, as it always has (the peak: old scene + the six buffers below), so its
+    // frames have not ended yet: a failure in here takes it away as an empty upload would.
+    SceneGuard guard{c, false};
+    Temps t(c);
+    float *d_pos = nullptr, *d_sc = nullptr, *d_op = nullptr, *d_rot = nullptr, *d_sh = nullptr, *d_cov = nullptr;
+    HIP_TRY(c, t.alloc(&d_pos, sizeof(float) * 4 * n));
+    HIP_TRY(c, t.alloc(&d_sc, sizeof(float) * 3 * n));
+    HIP_TRY(c, t.alloc(&d_op, sizeof(float) * n));
+    HIP_TRY(c, t.alloc(&d_rot, sizeof(float) * 4 * n));
+    HIP_TRY(c, t.alloc(&d_sh, sizeof(float) * 48 * n));
+    HIP_TRY(c, t.alloc(&d_cov, sizeof(float) * 9 * n));
+    // cov3d first, on the same stream: K0 behind the decode (GaussianList::from_vec), or zeros (Gaussian::new)
+    HIP_TRY(c, ply_decode_now(c, *lay, d_rows, d_pos, d_sc, d_op, d_rot, d_sh, producer_stream));
+    if (compute_cov3d) {
+        launch_cov3d(c->stream, n, d_sc, d_rot, d_cov);
+        HIP_TRY(c, hipGetLastError());
+    } else {
+        HIP_TRY(c, hipMemsetAsync(d_cov, 0, sizeof(float) * 9 * n, c->stream));
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    // scales and rotations have served: they go before the upload makes the scene's buffers; the other four it reads
+    t.release(d_sc);
+    t.release(d_rot);
+    guard.armed = false;           // (the upload has a guard of its own)
+    return splat_upload_scene_device(c, n, d_pos, d_cov, d_op, d_sh, nullptr);
+}
+
+// (debug, not part of the ABI)  Device time of the decode, the sequential sum and the subtraction inside the most recent
+// splat_decode_ply_device / splat_upload_ply_device, in milliseconds.
+int splat_debug_ply_ms(splat_ctx* c, double ms[3]) {
+    if (!c || !ms) return SPLAT_ERR_INVALID;
+    for (int k = 0; k < 3; ++k) ms[k] = c->ply_ms[k];
+    return SPLAT_OK;
+}
+
+int splat_get_scene_layout(splat_ctx* c, uint32_t* orig_out, uint64_t n, float* bounds_out, uint64_t n_blocks) {
+    if (!c) return SPLAT_ERR_INVALID;
+    if (n != c->n || n_blocks != (c->n + 255) / 256) return fail(c, SPLAT_ERR_INVALID, "scene layout size mismatch");
+    if (n == 0) return SPLAT_OK;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    static_assert(sizeof(BlockBounds) == 8 * sizeof(float), "bounds_out is 8 floats per block");
+    if (orig_out) HIP_TRY(c, hipMemcpy(orig_out, c->orig, sizeof(unsigned int) * n, hipMemcpyDeviceToHost));
+    if (bounds_out) HIP_TRY(c, hipMemcpy(bounds_out, c->bounds, sizeof(BlockBounds) * n_blocks, hipMemcpyDeviceToHost));
+    return SPLAT_OK;
+}
+
+int splat_compute_cov3d(splat_ctx* c, uint64_t n, const float* scales3, const float* rot4, float* cov3d_out) {
+    if (!c) return SPLAT_ERR_INVALID;
+    if (n == 0) return SPLAT_OK;
+    if (!scales3 || !rot4 || !cov3d_out) return fail(c, SPLAT_ERR_INVALID, "NULL pointer");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    Temps t(c);
+    float *d_s = nullptr, *d_r = nullptr, *d_o = nullptr;
+    HIP_TRY(c, t.alloc(&d_s, sizeof(float) * 3 * n));
+    HIP_TRY(c, t.alloc(&d_r, sizeof(float) * 4 * n));
+    HIP_TRY(c, t.alloc(&d_o, sizeof(float) * 9 * n));
+    HIP_TRY(c, hipMemcpyAsync(d_s, scales3, sizeof(float) * 3 * n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_r, rot4, sizeof(float) * 4 * n, hipMemcpyHostToDevice, c->stream));
+    launch_cov3d(c->stream, n, d_s, d_r, d_o);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(cov3d_out, d_o, sizeof(float) * 9 * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SPLAT_OK;
+}
+
+int splat_compute_cov3d_device(splat_ctx* c, uint64_t n, const void* d_scales3, const void* d_rot4, void* d_cov3d_out,
+                               void* producer_stream) {
+    if (!c) return SPLAT_ERR_INVALID;
+    if (n == 0) return SPLAT_OK;
+    if (!d_scales3 || !d_rot4 || !d_cov3d_out) return fail(c, SPLAT_ERR_INVALID, "NULL pointer");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    HIP_TRY(c, follow_producer(c, producer_stream));
+    launch_cov3d(c->stream, n, (const float*)d_scales3, (const float*)d_rot4, (float*)d_cov3d_out);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SPLAT_OK;
+}
+
+}  // extern "C"

@@ -7,7 +7,7 @@
 //
 // The order of the scene (orig[]) stays as the last upload left it.  A frame does not depend on it -- depth ties are settled
 // through orig[] and the bounds only cull -- so the frames that follow are those of a fresh upload of the edited arrays.
-// The bounds are block_bounds' of splat_api.hip, bit for bit: the planes hold the very floats the caller's buffers held.
+// The bounds are block_bounds' of splat_scene.hip, bit for bit: the planes hold the very floats the caller's buffers held.
 #include "splat_internal.h"
 
 namespace splat {

@@ -33,7 +33,7 @@ def _elf_sections(blob):
 
 
 def code_objects(path):
-    """{triple: bytes} of the offload bundle inside a host library."""
+    """{triple: [bytes, ...]} of the offload bundles inside a host library, in link order."""
     blob = open(path, "rb").read()
     secs = _elf_sections(blob)
     if ".hip_fatbin" not in secs:
@@ -58,29 +58,34 @@ def code_objects(path):
     return out
 
 
+def object_kernels(obj):
+    """{kernel symbol: metadata dict} of one code object (an ELF, as code_objects returns them)."""
+    found = {}
+    for name, (typ, off, size) in _elf_sections(obj).items():
+        if typ != 7:         # SHT_NOTE
+            continue
+        p = off
+        while p < off + size:
+            namesz, descsz, ntype = struct.unpack_from("<III", obj, p)
+            p += 12
+            nname = obj[p:p + namesz]
+            p += (namesz + 3) & ~3
+            desc = obj[p:p + descsz]
+            p += (descsz + 3) & ~3
+            if ntype == NT_AMDGPU_METADATA and nname.startswith(b"AMDGPU"):
+                md = msgpack.unpackb(desc, raw=False, strict_map_key=False)
+                for k in md.get("amdhsa.kernels", []):
+                    found[k.get(".name", "?")] = k
+    return found
+
+
 def kernels(path, arch="gfx950"):
     """{kernel symbol (demangled name when the metadata has it): metadata dict} for the device code of `arch`."""
     found = {}
     for triple, objs in code_objects(path).items():
-        if arch not in triple:
-            continue
-        for obj in objs:
-            secs = _elf_sections(obj)
-            for name, (typ, off, size) in secs.items():
-                if typ != 7:         # SHT_NOTE
-                    continue
-                p = off
-                while p < off + size:
-                    namesz, descsz, ntype = struct.unpack_from("<III", obj, p)
-                    p += 12
-                    nname = obj[p:p + namesz]
-                    p += (namesz + 3) & ~3
-                    desc = obj[p:p + descsz]
-                    p += (descsz + 3) & ~3
-                    if ntype == NT_AMDGPU_METADATA and nname.startswith(b"AMDGPU"):
-                        md = msgpack.unpackb(desc, raw=False, strict_map_key=False)
-                        for k in md.get("amdhsa.kernels", []):
-                            found[k.get(".name", "?")] = k
+        if arch in triple:
+            for obj in objs:
+                found.update(object_kernels(obj))
     return found
 
 

@@ -7,5 +7,5 @@ name=$1; shift
 cd "$(dirname "$0")/../../splat_amd/csrc"
 mkdir -p ../ab
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -Wall -Wno-unused-result -Wno-bitwise-instead-of-logical \
-  -fno-slp-vectorize "$@" -shared -o ../ab/libsplat_$name.so splat_api.hip splat_kernels.hip splat_multi.hip splat_policy.cpp -ldl -lpthread
+  -fno-slp-vectorize "$@" -shared -o ../ab/libsplat_$name.so $(sed -n 's/^SRC = //p' Makefile) -ldl -lpthread
 ls -la ../ab/libsplat_$name.so
