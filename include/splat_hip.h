@@ -40,7 +40,8 @@ extern "C" {
 /* Added under version 7, with no change to any struct or earlier entry point: splat_decode_ply_device and
  * splat_upload_ply_device (and the splat_ply_layout they take).  A library of version 7 may predate them: a binding
  * that wants them finds them by symbol (dlsym / hasattr) and does without them where they are missing.  Likewise
- * splat_update_scene_device and splat_update_gaussians_device (and the SPLAT_FIELD_* bits they take). */
+ * splat_update_scene_device and splat_update_gaussians_device (and the SPLAT_FIELD_* bits they take), and
+ * splat_select_device and splat_selection_indices_device (and the splat_select_query and SPLAT_SEL_* values they take). */
 
 /* modes: bit flags, 0 = the default */
 #define SPLAT_MODE_EXACT 0       /* back-to-front, 8-bit truncation per splat as blend() does it; the exponential of
@@ -208,6 +209,62 @@ int splat_update_scene_device(splat_ctx* ctx, uint64_t n, uint32_t fields, const
  * written).  Duplicate indices are the caller's error: which row lands is unspecified per field; nothing faults. */
 int splat_update_gaussians_device(splat_ctx* ctx, uint64_t k, const void* d_index, uint32_t fields, const void* d_pos4,
                                   const void* d_cov3d, const void* d_opacity, const void* d_sh, void* producer_stream);
+
+/* The SELECTION such an edit works on, made on the GPU from the resident scene: one byte per Gaussian in the caller's device
+ * memory (d_selection: n bytes at any byte address, ORIGINAL index order, nonzero = selected -- a torch.uint8 or torch.bool
+ * tensor is one, so a caller may make or edit one itself; the library writes only 0 and 1), and from it the u32 indices
+ * splat_update_gaussians_device takes.  Nothing crosses PCIe but the count.  A Gaussian passes a query when EVERY test the
+ * query names passes (tests == 0: all pass), on its RESIDENT values -- those of the last upload and the edits since: */
+#define SPLAT_SEL_VOLUME  1   /* position inside a box / ellipsoid given in world space   */
+#define SPLAT_SEL_SCREEN  2   /* where the Gaussian lands on the target under `cam`       */
+#define SPLAT_SEL_DEPTH   4   /* view-space z under `cam` (splat_record.depth) in a range */
+#define SPLAT_SEL_OPACITY 8   /* resident opacity in a range                              */
+#define SPLAT_SEL_OP_SET 0        /* selection = pass            */
+#define SPLAT_SEL_OP_ADD 1        /* selection |= pass           */
+#define SPLAT_SEL_OP_SUBTRACT 2   /* selection &= !pass          */
+#define SPLAT_SEL_OP_INTERSECT 3  /* selection &= pass           */
+typedef struct {
+    uint32_t tests;            /* SPLAT_SEL_* bits; a Gaussian passes when EVERY named test passes; 0 = all pass */
+    uint32_t volume_shape;     /* 0 = box, 1 = ellipsoid */
+    float    world_to_unit[12];/* 3x4 row-major affine map, world -> the unit shape */
+    uint32_t screen_rule;      /* 0 = centre, 1 = touch */
+    int32_t  x0, y0, x1, y1;   /* inclusive pixel rectangle, clamped to the target by the library */
+    float    depth_min, depth_max;
+    float    opacity_min, opacity_max;
+} splat_select_query;
+/* With r the splat_record the vertex stage (K1) gives the Gaussian under `cam`, the context's conventions and its mode
+ * (SPLAT_MODE_CORRECTED_PROJECTION: the corrected chain) -- bit for bit the record a frame of that camera is made of, on
+ * the WHOLE target: a slab set on the context is ignored, so rank 0's context of a multi-GPU set serves as it is:
+ *   VOLUME   u_k = ((m[4k] x + m[4k+1] y) + m[4k+2] z) + m[4k+3] in f32, unfused, in this order, m = world_to_unit;
+ *            box: |u_k| <= 1 for k = 0, 1, 2; ellipsoid: (u0 u0 + u1 u1) + u2 u2 <= 1.  A NaN fails.
+ *   SCREEN   r is visible (not singular, all finite, inside the z-clip when the convention is on, covering at least one
+ *            sample of the target) and, with the rectangle clamped to [0, w-1] x [0, h-1] (empty: nothing passes),
+ *            centre rule: (float)x0 <= r.cx < (float)(x1 + 1), the same in y, and -- with d_pixel_mask, a w*h u8 device
+ *            image such as a painted lasso or brush -- mask[(int)r.cy * w + (int)r.cx] != 0;
+ *            touch rule: the covered range [r.px0, r.px1] x [r.py0, r.py1] meets the rectangle (no pixel mask with it).
+ *   DEPTH    depth_min <= r.depth <= depth_max, for every Gaussian, visible or not.  A NaN fails.
+ *   OPACITY  opacity_min <= opacity <= opacity_max.
+ * `op` combines the result with what d_selection holds: SET does not read it, the others read and write it (ADD and
+ * SUBTRACT leave the bytes of Gaussians that do not pass as they are).  *count_out (nullable): the Gaussians selected
+ * after the op.  cam may be NULL unless SCREEN or DEPTH is named; d_pixel_mask may be NULL.
+ * Both calls are synchronous like the uploads (producer_stream as for splat_upload_scene_device), ordered on the context's
+ * stream behind the frames in flight.  They READ the scene: the state kept from frame to frame, the inverse order and
+ * splat_device_bytes() are as before (temporaries live for the call).
+ * SPLAT_ERR_INVALID, before any device work: a NULL context or query, unknown bits in `tests`, an unknown op, volume_shape
+ * or screen_rule, SCREEN or DEPTH named with a NULL cam (SCREEN: or a target that is no integer size in [1, 65535]), a
+ * pixel mask with the touch rule, a NULL d_selection with a scene; SPLAT_ERR_NO_SCENE: no resident scene.
+ * The multi-GPU layer needs no counterpart: every rank holds the whole scene and slabs are ignored, so one rank's context
+ * (splat_multi_ctx) selects for all. */
+int splat_select_device(splat_ctx* ctx, const splat_select_query* q, const splat_camera* cam, const void* d_pixel_mask,
+                        uint32_t op, void* d_selection, uint64_t* count_out, void* producer_stream);
+/* The indices of the nonzero bytes of d_selection[0..n), ascending, as u32 into d_index_out (4-byte aligned, `capacity`
+ * entries): a valid d_index for splat_update_gaussians_device -- distinct and < n.  Needs no scene; d_selection may be any
+ * byte mask at any byte address.  *count_out = how many are selected; when that is more than `capacity`, the first
+ * `capacity` of them are written and the call still returns SPLAT_OK: compare the two.  n == 0: SPLAT_OK, count 0.
+ * SPLAT_ERR_INVALID: a NULL context or count_out, n >= 2^32, a NULL d_selection with n > 0, a NULL or misaligned
+ * d_index_out with n > 0 and capacity > 0. */
+int splat_selection_indices_device(splat_ctx* ctx, uint64_t n, const void* d_selection, void* d_index_out,
+                                   uint64_t capacity, uint64_t* count_out, void* producer_stream);
 
 /* Debug / stage parity: the stored scene order and K1 block bounds of the current scene.
  * orig_out: n u32 (slot j holds original Gaussian orig[j]); bounds_out: ceil(n/256) x 8 f32

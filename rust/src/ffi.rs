@@ -18,6 +18,15 @@ pub const SPLAT_FIELD_POS: u32 = 1;
 pub const SPLAT_FIELD_COV3D: u32 = 2;
 pub const SPLAT_FIELD_OPACITY: u32 = 4;
 pub const SPLAT_FIELD_SH: u32 = 8;
+// the tests a selection query names, and how its result combines with the selection (splat_select_device)
+pub const SPLAT_SEL_VOLUME: u32 = 1;
+pub const SPLAT_SEL_SCREEN: u32 = 2;
+pub const SPLAT_SEL_DEPTH: u32 = 4;
+pub const SPLAT_SEL_OPACITY: u32 = 8;
+pub const SPLAT_SEL_OP_SET: u32 = 0;
+pub const SPLAT_SEL_OP_ADD: u32 = 1;
+pub const SPLAT_SEL_OP_SUBTRACT: u32 = 2;
+pub const SPLAT_SEL_OP_INTERSECT: u32 = 3;
 // tuning options (splat_set_option / splat_get_option): equivalent schedules and storage sizes, never pixels
 pub const SPLAT_OPT_PIPELINE_DEPTH: i32 = 1;
 pub const SPLAT_OPT_FUSED_SORT_MAX: i32 = 2;
@@ -82,6 +91,18 @@ pub struct SplatPlyLayout {
     pub n: u64, pub stride: u32, pub offset: [i32; SPLAT_PLY_SLOTS],
 }
 
+// a selection query: a Gaussian passes when every test named in `tests` (SPLAT_SEL_* bits) passes; 0 = all pass
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct SplatSelectQuery {
+    pub tests: u32,
+    pub volume_shape: u32,                         // 0 = box, 1 = ellipsoid
+    pub world_to_unit: [f32; 12],                  // 3x4 row-major affine map, world -> the unit shape
+    pub screen_rule: u32,                          // 0 = centre, 1 = touch
+    pub x0: i32, pub y0: i32, pub x1: i32, pub y1: i32,    // inclusive pixel rectangle
+    pub depth_min: f32, pub depth_max: f32,
+    pub opacity_min: f32, pub opacity_max: f32,
+}
+
 #[repr(C)] #[derive(Clone, Copy, Default)]
 pub struct SplatRecord {
     pub cx: f32, pub cy: f32, pub hx: f32, pub hy: f32,
@@ -120,6 +141,14 @@ extern "C" {
     pub fn splat_update_gaussians_device(ctx: *mut SplatCtx, k: u64, d_index: *const c_void, fields: u32, d_pos4: *const c_void,
                                          d_cov3d: *const c_void, d_opacity: *const c_void, d_sh: *const c_void,
                                          producer_stream: *mut c_void) -> c_int;
+    // a selection made on the GPU from the resident scene (added under ABI 7, found by symbol like those above): d_selection = one
+    // byte per Gaussian in device memory, original index order, nonzero = selected; cam may be null unless SCREEN or DEPTH is
+    // named, d_pixel_mask (w*h u8, centre rule only) and count_out may be null; op = SPLAT_SEL_OP_*
+    pub fn splat_select_device(ctx: *mut SplatCtx, q: *const SplatSelectQuery, cam: *const SplatCamera, d_pixel_mask: *const c_void,
+                               op: u32, d_selection: *mut c_void, count_out: *mut u64, producer_stream: *mut c_void) -> c_int;
+    // ... and its indices, ascending, as u32: a d_index for splat_update_gaussians_device; *count_out may exceed capacity
+    pub fn splat_selection_indices_device(ctx: *mut SplatCtx, n: u64, d_selection: *const c_void, d_index_out: *mut c_void,
+                                          capacity: u64, count_out: *mut u64, producer_stream: *mut c_void) -> c_int;
     // debug / stage parity: the stored order (n u32) and the K1 block bounds (ceil(n/256) x 8 f32); either may be null
     pub fn splat_get_scene_layout(ctx: *mut SplatCtx, orig_out: *mut u32, n: u64, bounds_out: *mut f32, n_blocks: u64) -> c_int;
     pub fn splat_set_slab(ctx: *mut SplatCtx, tile_row0: i32, tile_row1: i32) -> c_int;

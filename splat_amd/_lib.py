@@ -44,6 +44,18 @@ class Record(C.Structure):
 # SPLAT_FIELD_*: the fields an in-place edit names (splat_update_scene_device, splat_update_gaussians_device)
 FIELD_POS, FIELD_COV3D, FIELD_OPACITY, FIELD_SH = 1, 2, 4, 8
 
+# SPLAT_SEL_*: the tests a selection query names, and how its result combines with the selection (splat_select_device)
+SEL_VOLUME, SEL_SCREEN, SEL_DEPTH, SEL_OPACITY = 1, 2, 4, 8
+SEL_OP_SET, SEL_OP_ADD, SEL_OP_SUBTRACT, SEL_OP_INTERSECT = 0, 1, 2, 3
+
+
+class SelectQuery(C.Structure):
+    """splat_select_query: a Gaussian passes when every test named in `tests` passes (0: all pass)"""
+    _fields_ = [("tests", C.c_uint32), ("volume_shape", C.c_uint32), ("world_to_unit", C.c_float * 12),
+                ("screen_rule", C.c_uint32), ("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32), ("y1", C.c_int32),
+                ("depth_min", C.c_float), ("depth_max", C.c_float), ("opacity_min", C.c_float), ("opacity_max", C.c_float)]
+
+
 PLY_SLOTS = 59
 # destination slots of splat_ply_layout.offset: (first slot, count) per buffer, and the PLY property that feeds each slot
 PLY_SLOT_POS, PLY_SLOT_SCALE, PLY_SLOT_OPACITY, PLY_SLOT_ROT, PLY_SLOT_SH = 0, 3, 6, 7, 11
@@ -76,6 +88,10 @@ SYMBOLS = [
     ("splat_update_scene_device", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("splat_update_gaussians_device", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p]),
+    ("splat_select_device", C.c_int, [C.c_void_p, C.POINTER(SelectQuery), C.POINTER(CameraC), C.c_void_p, C.c_uint32, C.c_void_p,
+                                      C.POINTER(C.c_uint64), C.c_void_p]),
+    ("splat_selection_indices_device", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
+                                                 C.c_void_p]),
     ("splat_get_scene_layout", C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint64, _fp, C.c_uint64]),
     ("splat_set_slab", C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     ("splat_tile_row_loads", C.c_int, [C.c_void_p, C.POINTER(CameraC), C.POINTER(C.c_uint64), C.c_int32]),

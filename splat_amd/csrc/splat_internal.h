@@ -1,5 +1,5 @@
 // splat_internal.h -- shared between the host files (splat_api.hip, splat_scene.hip) and the kernel files (splat_kernels.hip,
-// splat_ply.hip, splat_update.hip).
+// splat_ply.hip, splat_update.hip, splat_select.hip).
 #ifndef SPLAT_INTERNAL_H
 #define SPLAT_INTERNAL_H
 #include <hip/hip_runtime.h>
@@ -173,6 +173,32 @@ void launch_repack_indexed(hipStream_t s, uint64_t n, uint64_t k, const unsigned
 // ... and the bounds of the K1 blocks from the planes, as block_bounds computes them from the buffers; dirty != nullptr:
 // only the blocks whose byte is set, which is cleared
 void launch_plane_bounds(hipStream_t s, uint64_t n, const float4* planes, unsigned char* dirty, BlockBounds* bounds);
+
+// A selection made from the resident scene (splat_select.hip).  SelectView: the camera and conventions the vertex stage's
+// geometry half needs -- a frame's, without slab, binning or compositor state.  The query arrives checked, its rectangle
+// clamped to the target (x0 > x1 or y0 > y1: empty).  Thread j judges slot j and reads / writes selection[orig[j]]; *count
+// (zeroed by the caller) += the Gaussians selected after `op`.
+struct SelectView {
+    float view[16];
+    float proj[16];
+    float w, h;
+    float htanx, htany, focal;
+    float lowpass;
+    int y_up, sample_half, zclip;
+    float zmin, zmax;
+    int W, H;
+    int corrected;
+};
+void launch_select_query(hipStream_t s, uint64_t n, const float4* planes, const unsigned int* orig, const splat_select_query& q,
+                         const SelectView& v, const unsigned char* pixel_mask, uint32_t op, unsigned char* selection,
+                         unsigned int* count);
+// ... and its indices: the positions of the nonzero bytes of mask[0..n), ascending, the first `capacity` of them into out.
+// counts: selection_groups(mask, n) + 1 words of scratch; the last one receives how many bytes are nonzero.
+constexpr unsigned int SELECT_SPAN = 4096;      // bytes of the mask per workgroup, on 16-byte boundaries of the ADDRESS
+constexpr unsigned int SELECT_SCAN_ROUND = 256; // workgroup counts the scan takes per round
+inline uint64_t selection_groups(const void* mask, uint64_t n) { return (((uintptr_t)mask & 15u) + n + SELECT_SPAN - 1) / SELECT_SPAN; }
+void launch_selection_indices(hipStream_t s, uint64_t n, const unsigned char* mask, unsigned int* out, uint64_t capacity,
+                              unsigned int* counts);
 
 // ---- The per-frame launches take one argument block each, by const&.  The blocks are plain aggregates without defaults: a
 // caller value-initialises one (`ScanArgs a{};`) and what it does not set is zero / nullptr / false.  What travels together

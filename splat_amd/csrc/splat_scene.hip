@@ -1,6 +1,7 @@
 // splat_scene.hip -- everything that puts values into the resident scene: the uploads (host buffers, device buffers, PLY
-// rows), the in-place edits, K0 (cov3d) and the scene's layout read back.  Host side only, no device code: the kernels are
-// splat_kernels.hip's (order, bounds, packing), splat_ply.hip's and splat_update.hip's.  What the frame scheduler
+// rows), the in-place edits, K0 (cov3d) and the scene's layout read back -- and the selections read from it, which name the
+// Gaussians such an edit is for.  Host side only, no device code: the kernels are splat_kernels.hip's (order, bounds,
+// packing), splat_ply.hip's, splat_update.hip's and splat_select.hip's.  What the frame scheduler
 // (splat_api.hip) holds per scene is behind the seam of splat_context.h.
 #include <algorithm>
 #include <cmath>
@@ -170,6 +171,22 @@ hipError_t ensure_inverse(splat_ctx* c) {
     if (e != hipSuccess) { dfree(c->inv); c->upd_bad = nullptr; c->upd_dirty = nullptr; return e; }
     launch_inverse_order(c->stream, n, c->orig, c->inv);
     return hipGetLastError();
+}
+
+// what splat_select_device refuses before it looks at the context or touches HIP; nullptr: nothing
+constexpr uint32_t SEL_TESTS_ALL = SPLAT_SEL_VOLUME | SPLAT_SEL_SCREEN | SPLAT_SEL_DEPTH | SPLAT_SEL_OPACITY;
+const char* select_refusal(const splat_select_query* q, const splat_camera* cam, const void* pixel_mask, uint32_t op) {
+    if (!q) return "NULL query";
+    if (q->tests & ~SEL_TESTS_ALL) return "unknown bits in tests";
+    if (op > SPLAT_SEL_OP_INTERSECT) return "unknown op";
+    if (q->volume_shape > 1u) return "unknown volume_shape";
+    if (q->screen_rule > 1u) return "unknown screen_rule";
+    if ((q->tests & (SPLAT_SEL_SCREEN | SPLAT_SEL_DEPTH)) && !cam) return "SCREEN or DEPTH named without a camera";
+    if ((q->tests & SPLAT_SEL_SCREEN) && (!(cam->w >= 1.0f) || !(cam->h >= 1.0f) || cam->w > 65535.0f || cam->h > 65535.0f ||
+                                          cam->w != std::floor(cam->w) || cam->h != std::floor(cam->h)))
+        return "camera w/h must be integers in [1, 65535]";
+    if ((q->tests & SPLAT_SEL_SCREEN) && q->screen_rule == 1u && pixel_mask) return "a pixel mask goes with the centre rule, not with touch";
+    return nullptr;
 }
 
 // what both PLY entry points refuse before they touch HIP; msg: why
@@ -354,6 +371,73 @@ int splat_update_gaussians_device(splat_ctx* c, uint64_t k, const void* d_index,
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     scene_edited(c);
+    return SPLAT_OK;
+}
+
+// The selection reads the scene as K1 does -- whole target, the context's conventions and mode -- and nothing of a frame's
+// state: no slot, no hint, no policy is touched, and what it allocates goes with the call.
+int splat_select_device(splat_ctx* c, const splat_select_query* q, const splat_camera* cam, const void* d_pixel_mask, uint32_t op,
+                        void* d_selection, uint64_t* count_out, void* producer_stream) {
+    // (the arguments are judged before the context is looked at, as the PLY entry points do it)
+    if (const char* why = select_refusal(q, cam, d_pixel_mask, op)) return fail(c, SPLAT_ERR_INVALID, why);
+    if (!c) return fail(c, SPLAT_ERR_INVALID, "NULL context");
+    if (c->n == 0) return fail(c, SPLAT_ERR_NO_SCENE, "no resident scene to select from");
+    if (!d_selection) return fail(c, SPLAT_ERR_INVALID, "NULL selection");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    int rc = ctx_quiesce(c);
+    if (rc != SPLAT_OK) return rc;
+    splat_select_query k = *q;
+    SelectView v{};
+    if (cam) {
+        std::copy(cam->view, cam->view + 16, v.view);
+        std::copy(cam->proj, cam->proj + 16, v.proj);
+        v.w = cam->w; v.h = cam->h; v.htanx = cam->htanx; v.htany = cam->htany; v.focal = cam->focal; v.lowpass = cam->lowpass;
+    }
+    v.y_up = c->cfg.y_up; v.sample_half = c->cfg.sample_half; v.zclip = c->cfg.zclip; v.zmin = c->cfg.zmin; v.zmax = c->cfg.zmax;
+    v.corrected = (c->cfg.mode & SPLAT_MODE_CORRECTED_PROJECTION) ? 1 : 0;
+    if (k.tests & SPLAT_SEL_SCREEN) {
+        v.W = (int)cam->w; v.H = (int)cam->h;
+        k.x0 = std::max(k.x0, 0); k.y0 = std::max(k.y0, 0);
+        k.x1 = std::min(k.x1, v.W - 1); k.y1 = std::min(k.y1, v.H - 1);
+    }
+    Temps t(c);
+    unsigned int* d_count = nullptr;
+    unsigned int count = 0;
+    HIP_TRY(c, t.alloc(&d_count, sizeof(unsigned int)));
+    HIP_TRY(c, hipMemsetAsync(d_count, 0, sizeof(unsigned int), c->stream));
+    HIP_TRY(c, follow_producer(c, producer_stream));
+    launch_select_query(c->stream, c->n, c->planes, c->orig, k, v, (k.tests & SPLAT_SEL_SCREEN) ? (const unsigned char*)d_pixel_mask : nullptr,
+                        op, (unsigned char*)d_selection, d_count);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(&count, d_count, sizeof count, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (count_out) *count_out = count;
+    return SPLAT_OK;
+}
+
+int splat_selection_indices_device(splat_ctx* c, uint64_t n, const void* d_selection, void* d_index_out, uint64_t capacity,
+                                   uint64_t* count_out, void* producer_stream) {
+    if (!c) return fail(c, SPLAT_ERR_INVALID, "NULL context");
+    if (!count_out) return fail(c, SPLAT_ERR_INVALID, "NULL count_out");
+    if (n >= (1ull << 32)) return fail(c, SPLAT_ERR_INVALID, "too many bytes in the selection (an index is 32-bit)");
+    if (n && !d_selection) return fail(c, SPLAT_ERR_INVALID, "NULL selection");
+    if (n && capacity && (!d_index_out || ((uintptr_t)d_index_out & 3u))) return fail(c, SPLAT_ERR_INVALID, "NULL or misaligned index buffer");
+    *count_out = 0;
+    if (n == 0) return SPLAT_OK;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    int rc = ctx_quiesce(c);
+    if (rc != SPLAT_OK) return rc;
+    Temps t(c);
+    unsigned int* d_counts = nullptr;
+    unsigned int count = 0;
+    const uint64_t g = selection_groups(d_selection, n);
+    HIP_TRY(c, t.alloc(&d_counts, sizeof(unsigned int) * (g + 1)));
+    HIP_TRY(c, follow_producer(c, producer_stream));
+    launch_selection_indices(c->stream, n, (const unsigned char*)d_selection, (unsigned int*)d_index_out, capacity, d_counts);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(&count, d_counts + g, sizeof count, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    *count_out = count;
     return SPLAT_OK;
 }
 

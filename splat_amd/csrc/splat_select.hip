@@ -1,0 +1,314 @@
+// splat_select.hip -- a selection made from the resident scene, and its indices (splat_select_device,
+// splat_selection_indices_device; gfx950).
+//
+//   select_kernel<LEVEL, CORRECTED>   one thread per stored slot: the query's tests on the resident values, combined with the
+//                                     caller's byte at selection[orig[slot]], and the count of what is selected afterwards
+//   mask_count_kernel                 how many bytes of a span of the mask are nonzero, per workgroup
+//   mask_scan_kernel                  one workgroup: the exclusive prefix sums of those counts, 256 of them a round
+//   mask_scatter_kernel               the positions of a span's nonzero bytes, written behind those of the spans before it
+//
+// The SCREEN test is the geometry half of K1 (preprocess_kernel of splat_kernels.hip) restated: the same f32 operations in
+// the same order (project_cov3d_to_screen, the conic, the half extents, NDC to pixels, visibility, covered_interval), built
+// with the same flags -- no contraction, correctly rounded division and square root -- so the same bits: a Gaussian is
+// selected by the very centre and covered range the frame draws it with (tests/test_gpu_select.py holds it to the oracle).
+// The compaction never waits on another workgroup: three launches, each reading what the one before it wrote.
+#include "splat_internal.h"
+
+namespace splat {
+
+// ---------------------------------------------------------------------------
+// K1's small helpers, as splat_kernels.hip has them (column-major; products accumulate left to right)
+// ---------------------------------------------------------------------------
+struct SelMat3 { float m[9]; };
+#define SM3(A, r, c) ((A).m[(c) * 3 + (r)])
+
+static __device__ __forceinline__ SelMat3 sel_mat3_mul(const SelMat3& a, const SelMat3& b) {
+    SelMat3 c;
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            float acc = SM3(a, i, 0) * SM3(b, 0, j);
+            acc = SM3(a, i, 1) * SM3(b, 1, j) + acc;
+            acc = SM3(a, i, 2) * SM3(b, 2, j) + acc;
+            SM3(c, i, j) = acc;
+        }
+    return c;
+}
+static __device__ __forceinline__ SelMat3 sel_mat3_t(const SelMat3& a) {
+    SelMat3 t;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) SM3(t, i, j) = SM3(a, j, i);
+    return t;
+}
+// row i of m * (x, y, z, w)
+static __device__ __forceinline__ float sel_mat4_row(const float* m, int i, float x, float y, float z, float w) {
+    float acc = m[0 + i] * x;
+    acc = m[4 + i] * y + acc;
+    acc = m[8 + i] * z + acc;
+    acc = m[12 + i] * w + acc;
+    return acc;
+}
+static __device__ __forceinline__ bool sel_finite(float v) { return fabsf(v) <= 3.402823466e+38f; }
+
+// Exactly covered pixel interval {p in [lo_lim,hi_lim] : |p + off - c| <= h}; false when empty.
+static __device__ __forceinline__ bool sel_covered_interval(float c, float h, float off, int lo_lim, int hi_lim, int* lo, int* hi) {
+    float flo = c - h - off, fhi = c + h - off;
+    if (!(fhi >= (float)lo_lim - 2.0f) || !(flo <= (float)hi_lim + 2.0f)) return false;
+    int a = (int)fmaxf(floorf(flo) - 1.0f, (float)lo_lim);
+    int b = (int)fminf(ceilf(fhi) + 1.0f, (float)hi_lim);
+#pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
+    while (a <= b && !(fabsf(((float)a + off) - c) <= h)) ++a;
+#pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
+    while (b >= a && !(fabsf(((float)b + off) - c) <= h)) --b;
+    if (a > b) return false;
+    *lo = a; *hi = b;
+    return true;
+}
+
+// The geometry half of the vertex stage for one Gaussian: centre, and the covered pixel range when it is visible on the
+// whole target (K1's `on_target`, the oracle's `visible`).  pc2 = view-space z (splat_record.depth).
+template <bool CORRECTED>
+static __device__ __forceinline__ bool sel_project(const SelectView& fc, float px, float py, float pz, const float (&c9)[9],
+                                                   float* cx_out, float* cy_out, int (&r)[4]) {
+    // project_cov3d_to_screen                                            src/gaussians.rs:114-161
+    float pc[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) pc[i] = sel_mat4_row(fc.view, i, px, py, pz, 1.0f);
+    float limx = 1.3f * fc.htanx, limy = 1.3f * fc.htany;
+    float txtz = pc[0] / pc[2], tytz = pc[1] / pc[2];
+    float tx = fminf(limx, fmaxf(-limx, txtz)) * pc[2];
+    float ty = fminf(limy, fmaxf(-limy, tytz)) * pc[2];
+    float tz = pc[2];
+    SelMat3 J;
+    SM3(J, 0, 0) = fc.focal / tz; SM3(J, 0, 1) = 0.0f;          SM3(J, 0, 2) = -(fc.focal * tx) / (tz * tz);
+    SM3(J, 1, 0) = 0.0f;          SM3(J, 1, 1) = fc.focal / tz; SM3(J, 1, 2) = -(fc.focal * ty) / (tz * tz);
+    SM3(J, 2, 0) = 0.0f;          SM3(J, 2, 1) = 0.0f;          SM3(J, 2, 2) = 0.0f;
+    SelMat3 Wm;   // viewmatrix.fixed_view::<3,3>(0,0).transpose()
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) SM3(Wm, a, b) = fc.view[a * 4 + b];
+    SelMat3 T = CORRECTED ? sel_mat3_mul(Wm, sel_mat3_t(J)) : sel_mat3_mul(Wm, J);
+    SelMat3 Sg;
+#pragma unroll
+    for (int e = 0; e < 9; ++e) Sg.m[e] = c9[e];
+    SelMat3 cov = sel_mat3_mul(sel_mat3_mul(sel_mat3_t(T), sel_mat3_t(Sg)), T);
+    float m11 = SM3(cov, 0, 0) + fc.lowpass, m21 = SM3(cov, 1, 0), m12 = SM3(cov, 0, 1), m22 = SM3(cov, 1, 1) + fc.lowpass;
+
+    // gaussian_vertex_shader                                             src/pipelines.rs:17-51
+    float det = m11 * m22 - m21 * m12;
+    float q[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) q[i] = sel_mat4_row(fc.proj, i, pc[0], pc[1], pc[2], pc[3]);
+    float ndcx = q[0] / q[3], ndcy = q[1] / q[3], ndcz = q[2] / q[3];
+    float ca = m22 / det, cb = -m12 / det, cc = m11 / det;
+    float hx = 3.0f * sqrtf(m11), hy = 3.0f * sqrtf(m22);
+    // euc: NDC -> target pixels
+    float cx = (ndcx * 0.5f + 0.5f) * fc.w;
+    float cy = fc.y_up ? (ndcy * -0.5f + 0.5f) * fc.h : (ndcy * 0.5f + 0.5f) * fc.h;
+    bool vis = !(det == 0.0f) && sel_finite(cx) && sel_finite(cy) && sel_finite(hx) && sel_finite(hy) && sel_finite(ca) &&
+               sel_finite(cb) && sel_finite(cc) && sel_finite(ndcz);
+    if (vis && fc.zclip) vis = (fc.zmin <= ndcz) && (ndcz <= fc.zmax);
+    const float off = fc.sample_half ? 0.5f : 0.0f;
+    *cx_out = cx; *cy_out = cy;
+    return vis && sel_covered_interval(cx, hx, off, 0, fc.W - 1, &r[0], &r[1]) &&
+           sel_covered_interval(cy, hy, off, 0, fc.H - 1, &r[2], &r[3]);
+}
+
+// ---------------------------------------------------------------------------
+// The predicate.  LEVEL: what the named tests need of the camera -- 0: nothing (VOLUME, OPACITY: plane 0 alone is read),
+// 1: view-space z (DEPTH: one row of the view matrix), 2: the projected Gaussian (SCREEN: planes 0-3).  No SH is loaded.
+// The byte of a Gaussian belongs to the one thread that holds its slot (orig is a permutation): nothing races.
+// ---------------------------------------------------------------------------
+template <int LEVEL, bool CORRECTED>
+__global__ __launch_bounds__(256) void select_kernel(uint64_t n, const float4* __restrict__ planes, const unsigned int* __restrict__ orig,
+                                                     splat_select_query q, SelectView fc, const unsigned char* __restrict__ pixel_mask,
+                                                     uint32_t op, unsigned char* selection, unsigned int* __restrict__ count) {
+    __shared__ unsigned int wsel[4];
+    const uint64_t j = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    bool sel = false;
+    if (j < n) {
+        const float4 p0 = planes[j];                           // x y z | opacity
+        bool pass = true;
+        if (q.tests & SPLAT_SEL_VOLUME) {
+            const float* m = q.world_to_unit;
+            float u[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) u[k] = ((m[4 * k] * p0.x + m[4 * k + 1] * p0.y) + m[4 * k + 2] * p0.z) + m[4 * k + 3];
+            if (q.volume_shape == 0u) pass = (fabsf(u[0]) <= 1.0f) && (fabsf(u[1]) <= 1.0f) && (fabsf(u[2]) <= 1.0f);
+            else pass = ((u[0] * u[0] + u[1] * u[1]) + u[2] * u[2]) <= 1.0f;
+        }
+        if (q.tests & SPLAT_SEL_OPACITY) pass = pass && (q.opacity_min <= p0.w) && (p0.w <= q.opacity_max);
+        if (LEVEL >= 1 && (q.tests & SPLAT_SEL_DEPTH)) {
+            const float z = sel_mat4_row(fc.view, 2, p0.x, p0.y, p0.z, 1.0f);
+            pass = pass && (q.depth_min <= z) && (z <= q.depth_max);
+        }
+        if (LEVEL >= 2) {                                      // (launched only with SCREEN named)
+            const float4 c0 = planes[n + j], c1 = planes[2 * n + j];
+            const float c8 = planes[3 * n + j].x;
+            const float c9[9] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w, c8};
+            float cx, cy; int r[4] = {1, 0, 1, 0};
+            bool hit = sel_project<CORRECTED>(fc, p0.x, p0.y, p0.z, c9, &cx, &cy, r) && q.x0 <= q.x1 && q.y0 <= q.y1;
+            if (hit) {
+                if (q.screen_rule == 0u) {
+                    hit = ((float)q.x0 <= cx) && (cx < (float)(q.x1 + 1)) && ((float)q.y0 <= cy) && (cy < (float)(q.y1 + 1));
+                    // (inside the clamped rectangle: 0 <= (int)cx < W and 0 <= (int)cy < H)
+                    if (hit && pixel_mask) hit = pixel_mask[(size_t)(int)cy * (size_t)fc.W + (size_t)(int)cx] != 0;
+                } else {
+                    hit = r[0] <= q.x1 && r[1] >= q.x0 && r[2] <= q.y1 && r[3] >= q.y0;
+                }
+            }
+            pass = pass && hit;
+        }
+        unsigned char* const b = selection + orig[j];
+        if (op == SPLAT_SEL_OP_SET) { sel = pass; *b = (unsigned char)(pass ? 1 : 0); }
+        else {
+            const bool old = *b != 0;
+            if (op == SPLAT_SEL_OP_ADD) { sel = old || pass; if (pass) *b = (unsigned char)1; }
+            else if (op == SPLAT_SEL_OP_SUBTRACT) { sel = old && !pass; if (pass) *b = (unsigned char)0; }
+            else { sel = old && pass; *b = (unsigned char)(sel ? 1 : 0); }
+        }
+    }
+    // the count: a ballot and a popcount per wave, the four summed in LDS, one atomic per workgroup that selected any
+    const unsigned long long m = __ballot(sel);
+    if ((threadIdx.x & 63u) == 0u) wsel[threadIdx.x >> 6] = (unsigned int)__popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned int t = (wsel[0] + wsel[1]) + (wsel[2] + wsel[3]);
+        if (t) atomicAdd(count, t);
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Compaction.  The mask may start at any byte address: it is read on the 16-byte boundaries of its ADDRESS.  With
+// head = address & 15, chunk c holds the mask's bytes 16 c - head .. 16 c - head + 15; thread t of workgroup g takes chunk
+// 256 g + t -- one 16-byte load where the chunk lies inside the mask, byte loads of the bytes that do where it does not (the
+// first chunk and the last): nothing outside mask[0..n) is read.  bits: bit k set = byte k of the chunk is nonzero.
+// ---------------------------------------------------------------------------
+static __device__ __forceinline__ unsigned int nonzero_bytes(unsigned int w) {     // one bit per nonzero byte of a word
+    return (unsigned int)((w & 0x000000ffu) != 0u) | ((unsigned int)((w & 0x0000ff00u) != 0u) << 1) |
+           ((unsigned int)((w & 0x00ff0000u) != 0u) << 2) | ((unsigned int)((w & 0xff000000u) != 0u) << 3);
+}
+// first: the mask index of the chunk's byte 0 (negative in the first chunk of a mask that starts off a boundary)
+static __device__ __forceinline__ unsigned int chunk_bits(const unsigned char* __restrict__ mask, uint64_t n, unsigned int head,
+                                                          uint64_t chunk, int64_t* first) {
+    const int64_t i0 = (int64_t)(chunk * 16u) - (int64_t)head;
+    *first = i0;
+    if (i0 >= (int64_t)n) return 0u;
+    if (i0 >= 0 && i0 + 16 <= (int64_t)n) {
+        const uint4 v = *reinterpret_cast<const uint4*>(mask + i0);                 // (16-byte aligned by construction)
+        return nonzero_bytes(v.x) | (nonzero_bytes(v.y) << 4) | (nonzero_bytes(v.z) << 8) | (nonzero_bytes(v.w) << 12);
+    }
+    unsigned int bits = 0u;
+    for (int k = 0; k < 16; ++k) {
+        const int64_t i = i0 + k;
+        if (i >= 0 && i < (int64_t)n && mask[i] != 0) bits |= 1u << k;
+    }
+    return bits;
+}
+// Where a lane's selected bytes rank among its wave's, in index order (lane by lane, byte by byte): for each of the sixteen
+// byte positions a ballot of the lanes that hold a selected byte there; those of the lanes below (mbcnt) come first.
+// *total: the wave's selected bytes.
+static __device__ __forceinline__ unsigned int wave_rank(unsigned int bits, unsigned int* total) {
+    unsigned int rank = 0u, tot = 0u;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const unsigned long long b = __ballot((bits >> k) & 1u);
+        rank += __builtin_amdgcn_mbcnt_hi((unsigned int)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)b, 0u));
+        tot += (unsigned int)__popcll(b);
+    }
+    *total = tot;
+    return rank;
+}
+
+__global__ __launch_bounds__(256) void mask_count_kernel(uint64_t n, const unsigned char* __restrict__ mask, unsigned int head,
+                                                         unsigned int* __restrict__ counts) {
+    __shared__ unsigned int wtot[4];
+    int64_t first;
+    const unsigned int bits = chunk_bits(mask, n, head, (uint64_t)blockIdx.x * 256u + threadIdx.x, &first);
+    unsigned int tot;
+    (void)wave_rank(bits, &tot);
+    if ((threadIdx.x & 63u) == 0u) wtot[threadIdx.x >> 6] = tot;
+    __syncthreads();
+    if (threadIdx.x == 0) counts[blockIdx.x] = (wtot[0] + wtot[1]) + (wtot[2] + wtot[3]);
+}
+
+// counts[0..g) -> their exclusive prefix sums, counts[g] = the total.  ONE workgroup, SELECT_SCAN_ROUND counts a round with
+// the sum so far carried from round to round (every thread carries the same one): as many rounds as it takes.
+__global__ __launch_bounds__(256) void mask_scan_kernel(unsigned int g, unsigned int* __restrict__ counts) {
+    static_assert(SELECT_SCAN_ROUND == 256u, "one count per thread and round");
+    __shared__ unsigned int wsum[4];
+    const unsigned int lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    unsigned int carry = 0u;
+    for (unsigned int base = 0u; base < g; base += SELECT_SCAN_ROUND) {            // (uniform)
+        const unsigned int i = base + threadIdx.x;
+        const unsigned int v = i < g ? counts[i] : 0u;
+        unsigned int inc = v;
+#pragma unroll
+        for (int k = 1; k < 64; k <<= 1) {
+            const unsigned int below = __shfl_up(inc, k);
+            if (lane >= (unsigned int)k) inc += below;
+        }
+        if (lane == 63u) wsum[w] = inc;
+        __syncthreads();
+        unsigned int before = 0u;
+        for (unsigned int k = 0; k < w; ++k) before += wsum[k];
+        const unsigned int round = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+        if (i < g) counts[i] = carry + before + (inc - v);
+        carry += round;
+        __syncthreads();                                       // (wsum is written again by the next round)
+    }
+    if (threadIdx.x == 0) counts[g] = carry;
+}
+
+// offsets: the scanned counts.  A lane's selected bytes land at offsets[workgroup] + those of the waves before its own +
+// its rank in the wave, in index order: the output is ascending.  Entries beyond `capacity` are not written.
+__global__ __launch_bounds__(256) void mask_scatter_kernel(uint64_t n, const unsigned char* __restrict__ mask, unsigned int head,
+                                                           const unsigned int* __restrict__ offsets, unsigned int* __restrict__ out,
+                                                           uint64_t capacity) {
+    __shared__ unsigned int wtot[4];
+    int64_t first;
+    unsigned int bits = chunk_bits(mask, n, head, (uint64_t)blockIdx.x * 256u + threadIdx.x, &first);
+    unsigned int tot;
+    const unsigned int rank = wave_rank(bits, &tot);
+    const unsigned int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63u) == 0u) wtot[w] = tot;
+    __syncthreads();
+    uint64_t pos = (uint64_t)offsets[blockIdx.x] + rank;
+    for (unsigned int k = 0; k < w; ++k) pos += wtot[k];
+    while (bits != 0u && pos < capacity) {
+        const int k = __builtin_ctz(bits);
+        bits &= bits - 1u;
+        out[pos++] = (unsigned int)(first + k);
+    }
+}
+
+// ---------------------------------------------------------------------------
+// launch wrappers
+// ---------------------------------------------------------------------------
+void launch_select_query(hipStream_t s, uint64_t n, const float4* planes, const unsigned int* orig, const splat_select_query& q,
+                         const SelectView& v, const unsigned char* pixel_mask, uint32_t op, unsigned char* selection,
+                         unsigned int* count) {
+    if (!n) return;
+    const dim3 grid((unsigned int)((n + 255) / 256)), block(256);
+    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, s, n, planes, orig, q, v, pixel_mask, op, selection, count); };
+    if (q.tests & SPLAT_SEL_SCREEN) { if (v.corrected) go(select_kernel<2, true>); else go(select_kernel<2, false>); }
+    else if (q.tests & SPLAT_SEL_DEPTH) go(select_kernel<1, false>);
+    else go(select_kernel<0, false>);
+}
+
+void launch_selection_indices(hipStream_t s, uint64_t n, const unsigned char* mask, unsigned int* out, uint64_t capacity,
+                              unsigned int* counts) {
+    if (!n) return;
+    static_assert(SELECT_SPAN == 256u * 16u, "a workgroup's span is one 16-byte chunk per thread");
+    const unsigned int head = (unsigned int)((uintptr_t)mask & 15u);
+    const unsigned int g = (unsigned int)selection_groups(mask, n);                // (n < 2^32: at most 2^20 + 1)
+    hipLaunchKernelGGL(mask_count_kernel, dim3(g), dim3(256), 0, s, n, mask, head, counts);
+    hipLaunchKernelGGL(mask_scan_kernel, dim3(1), dim3(256), 0, s, g, counts);
+    if (capacity && out) hipLaunchKernelGGL(mask_scatter_kernel, dim3(g), dim3(256), 0, s, n, mask, head, (const unsigned int*)counts, out, capacity);
+}
+
+}  // namespace splat

@@ -46,6 +46,18 @@ def _device_address(a, what, floats, device, any_dtype=False):
     return int(a.data_ptr())
 
 
+def _byte_mask_address(a, what, count, device):
+    """Device address of a byte mask (a selection, a pixel mask): as _device_address, of any dtype one byte wide (uint8,
+    bool) and `count` elements where it can tell."""
+    p = _device_address(a, what, None, device, any_dtype=True)
+    if not isinstance(a, int):
+        if hasattr(a, "element_size") and int(a.element_size()) != 1:
+            raise TypeError("%s: one byte per element expected, got %s" % (what, getattr(a, "dtype", None)))
+        if hasattr(a, "numel") and int(a.numel()) != count:
+            raise ValueError("%s: %d bytes expected, got %d" % (what, count, int(a.numel())))
+    return p
+
+
 def _count_of(a, per, n):
     """Gaussians in buffer `a` of `per` floats each: from its numel() unless the caller said n=."""
     if n is not None:
@@ -189,6 +201,83 @@ class Renderer:
         st = _producer_stream(stream, (index, positions, cov3d, opacities, sh))
         self._check(self._L.splat_update_gaussians_device(self._h, k, C.c_void_p(pi), mask, *[C.c_void_p(p) for p in ptrs],
                                                           C.c_void_p(st)))
+
+    # ---- selections ---------------------------------------------------------------------
+    _SEL_OPS = {"set": _lib.SEL_OP_SET, "add": _lib.SEL_OP_ADD, "subtract": _lib.SEL_OP_SUBTRACT, "intersect": _lib.SEL_OP_INTERSECT}
+
+    def select(self, selection, cam_c=None, *, box=None, ellipsoid=None, rect=None, rule="centre", pixel_mask=None, depth=None,
+               opacity=None, op="set", stream=None):
+        """splat_select_device: which Gaussians of the resident scene pass every test named, into `selection` -- one byte per
+        Gaussian in device memory, original index order, nonzero = selected (a device address or an object with data_ptr():
+        a torch.uint8 / torch.bool tensor of n elements).  box / ellipsoid: a 3x4 row-major affine map from world space to
+        the unit box / unit sphere; rect=(x0, y0, x1, y1): inclusive pixels of the target of cam_c, by rule "centre" (where
+        the Gaussian's centre lands; pixel_mask: a w*h uint8 device image it must also hit) or "touch" (its covered pixels
+        meet the rectangle); depth=(min, max): view-space z under cam_c; opacity=(min, max).  op: "set", "add",
+        "subtract", "intersect" with what `selection` holds.  The screen test sees the very records a frame of cam_c is made
+        of.  Returns how many Gaussians are selected after the op."""
+        q = _lib.SelectQuery()
+        if box is not None and ellipsoid is not None:
+            raise ValueError("box and ellipsoid: one volume per query (combine two queries with op=)")
+        vol = box if box is not None else ellipsoid
+        if vol is not None:
+            m = np.ascontiguousarray(vol, f32)
+            if m.shape != (3, 4):
+                raise ValueError("box / ellipsoid: a 3x4 array expected, got shape %r" % (m.shape,))
+            q.tests |= _lib.SEL_VOLUME
+            q.volume_shape = 0 if box is not None else 1
+            q.world_to_unit[:] = [float(x) for x in m.ravel()]
+        if rule not in ("centre", "touch"):
+            raise ValueError("rule: 'centre' or 'touch', got %r" % (rule,))
+        if pixel_mask is not None and rect is None:
+            raise ValueError("pixel_mask: goes with rect= (the whole target: rect=(0, 0, w - 1, h - 1))")
+        if rect is not None:
+            if pixel_mask is not None and rule == "touch":
+                raise ValueError("pixel_mask goes with rule='centre', not with 'touch'")
+            q.tests |= _lib.SEL_SCREEN
+            q.screen_rule = 0 if rule == "centre" else 1
+            q.x0, q.y0, q.x1, q.y1 = [int(x) for x in rect]
+        if depth is not None:
+            q.tests |= _lib.SEL_DEPTH
+            q.depth_min, q.depth_max = float(depth[0]), float(depth[1])
+        if opacity is not None:
+            q.tests |= _lib.SEL_OPACITY
+            q.opacity_min, q.opacity_max = float(opacity[0]), float(opacity[1])
+        if op not in self._SEL_OPS:
+            raise ValueError("op: one of %s, got %r" % (sorted(self._SEL_OPS), op))
+        if (q.tests & (_lib.SEL_SCREEN | _lib.SEL_DEPTH)) and cam_c is None:
+            raise ValueError("rect= and depth= need cam_c")
+        dev = int(self.config.device)
+        ps = _byte_mask_address(selection, "selection", self.n, dev)
+        pm = _byte_mask_address(pixel_mask, "pixel_mask", int(cam_c.w) * int(cam_c.h), dev) if pixel_mask is not None else 0
+        st = _producer_stream(stream, (selection, pixel_mask))
+        count = C.c_uint64()
+        self._check(self._L.splat_select_device(self._h, C.byref(q), C.byref(cam_c) if cam_c is not None else None, C.c_void_p(pm),
+                                                self._SEL_OPS[op], C.c_void_p(ps), C.byref(count), C.c_void_p(st)))
+        return int(count.value)
+
+    def selection_indices(self, selection, out, stream=None, n=None, capacity=None):
+        """splat_selection_indices_device: the indices of the nonzero bytes of `selection` (n bytes: n= with a plain address,
+        default the resident scene's n), ascending, as uint32 into `out` (device memory of `capacity` entries: capacity= with a
+        plain address) -- what update_indexed takes as index.  Returns how many are selected; when that is more than
+        capacity, the first `capacity` of them were written."""
+        dev = int(self.config.device)
+        if n is None:
+            n = int(selection.numel()) if (not isinstance(selection, int) and hasattr(selection, "numel")) else self.n
+        n = int(n)
+        ps = _byte_mask_address(selection, "selection", n, dev)
+        if capacity is None:
+            if isinstance(out, int) or not hasattr(out, "numel"):
+                raise TypeError("capacity= is required with a plain device address")
+            capacity = int(out.numel())
+        capacity = int(capacity)
+        if not isinstance(out, int) and hasattr(out, "element_size") and int(out.element_size()) != 4:
+            raise TypeError("out: 32-bit indices expected, got %s" % getattr(out, "dtype", None))
+        po = _device_address(out, "out", None, dev, any_dtype=True)
+        st = _producer_stream(stream, (selection, out))
+        count = C.c_uint64()
+        self._check(self._L.splat_selection_indices_device(self._h, n, C.c_void_p(ps), C.c_void_p(po), capacity, C.byref(count),
+                                                           C.c_void_p(st)))
+        return int(count.value)
 
     def compute_cov3d_device(self, scales, rotations, out, stream=None, n=None):
         """splat_compute_cov3d_device: kernel K0 from device buffers (scales [n,3], rotations [n,4]) into a device buffer
