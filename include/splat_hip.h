@@ -338,6 +338,9 @@ int splat_sync(splat_ctx* ctx);
  * splat_render_device.  With a slab set, only the slab's rows are cleared and rendered. */
 int splat_render_frame_device(splat_ctx* ctx, const splat_camera* cam, void* d_argb, int32_t sync, splat_stats* stats);
 uint64_t splat_frames_dropped(const splat_ctx* ctx);  /* frames skipped on the device since splat_create (redone or reported) */
+/* *n = frames since splat_create that were composited from RETAINED LISTS (SPLAT_OPT_RETAIN_LISTS): the lists an earlier frame
+ * of the same camera left in order in memory -- no preprocess, scan, selection or sort of their own. */
+int splat_frames_retained(splat_ctx* ctx, uint64_t* n);
 /* Device memory this context holds right now (scene planes, per-frame buffers of its frame slots, key buffers, images it
  * allocated); *peak (nullable) = the most it has held since splat_create. */
 uint64_t splat_device_bytes(const splat_ctx* ctx, uint64_t* peak);
@@ -445,6 +448,12 @@ int splat_set_frame_overlap(splat_ctx* ctx, int32_t n);
                                             does not (those waves are not counted as n_fallback).  Exactness never rests on it.  Exact modes only (not with
                                             SPLAT_MODE_FAST, whose frame depends on where a walk starts).
                                             1 = on (default), 0 = off (SPLAT_START_REFINE)                                         */
+#define SPLAT_OPT_RETAIN_LISTS 25        /* a camera at rest composites from the lists an earlier frame left in order: once the camera
+                                            the calls receive has been the same, byte for byte, for three frames, one frame stores its
+                                            sorted lists back to memory (64 MB on C3, once) and the frames behind it launch the compositor
+                                            alone -- until the camera, the scene (upload, edit), the slab, the target, an option or the
+                                            storage changes.  Same pixels.  Not with a frame overlap of 2, not with two-pass binning.
+                                            1 = on (default), 0 = off (SPLAT_RETAIN; include/splat_retain.h)                        */
 int splat_set_option(splat_ctx* ctx, int32_t option, double value);
 int splat_get_option(const splat_ctx* ctx, int32_t option, double* value);
 void* splat_stream(splat_ctx* ctx);                   /* the hipStream_t the kernels run on */
@@ -454,7 +463,11 @@ int splat_set_stream(splat_ctx* ctx, void* hip_stream);
  * kernels' own streams around the launches: ms[0..5] = preprocess, scan, emit, sort, composite,
  * status read-back; *frames = frames that carried events.  Event records cost queue bubbles, so
  * only every SPLAT_TIMING_EVERY-th frame (default 8) of an asynchronous run carries them, plus every
- * frame rendered with a stats pointer; averages = ms[k] / *frames.  Waits for outstanding frames. */
+ * frame rendered with a stats pointer; averages = ms[k] / *frames.  Waits for outstanding frames.
+ * With retained lists (SPLAT_OPT_RETAIN_LISTS): a retained frame that carries events adds to ms[4] and ms[5] only and counts in
+ * *frames -- it has no preprocess, scan, emit or sort -- so over a camera at rest ms[0..3] / *frames tend to 0.  The frame that
+ * stores the lists (one per rest) always carries the events, beyond the sampling: *frames may exceed the sampled count by one
+ * per rest, and ms[0..3] over a span that contains that frame are ITS kernels' times, not an average over the span's frames. */
 int splat_get_timing(splat_ctx* ctx, double ms[6], uint64_t* frames, int32_t reset);
 
 /* Debug / stage parity: results of the last frame.  splat_get_tile_lists needs a frame rendered WITH a stats pointer

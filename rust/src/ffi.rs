@@ -52,6 +52,7 @@ pub const SPLAT_OPT_COUNT_FIRST: i32 = 21;
 pub const SPLAT_OPT_LARGE_SPLAT_TILES: i32 = 22;
 pub const SPLAT_OPT_LARGE_LIST_MIN: i32 = 23;
 pub const SPLAT_OPT_START_REFINE: i32 = 24;
+pub const SPLAT_OPT_RETAIN_LISTS: i32 = 25;
 /// SPLAT_ABI_VERSION of the header this file mirrors; compared with splat_abi_version() before the first call
 pub const SPLAT_ABI_VERSION: u32 = 7;
 
@@ -162,6 +163,7 @@ extern "C" {
                                      sync: i32, stats: *mut SplatStats) -> c_int;
     pub fn splat_sync(ctx: *mut SplatCtx) -> c_int;
     pub fn splat_frames_dropped(ctx: *const SplatCtx) -> u64;
+    pub fn splat_frames_retained(ctx: *mut SplatCtx, n: *mut u64) -> c_int;
     pub fn splat_device_bytes(ctx: *const SplatCtx, peak: *mut u64) -> u64;
     pub fn splat_binning_mode(ctx: *mut SplatCtx) -> i64;
     pub fn splat_set_frame_overlap(ctx: *mut SplatCtx, n: i32) -> c_int;   // 2: frames to different images composite side by side

@@ -101,6 +101,7 @@ SYMBOLS = [
     ("splat_render_frame_device", C.c_int, [C.c_void_p, C.POINTER(CameraC), C.c_void_p, C.c_int32, C.POINTER(Stats)]),
     ("splat_sync", C.c_int, [C.c_void_p]),
     ("splat_frames_dropped", C.c_uint64, [C.c_void_p]),
+    ("splat_frames_retained", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     ("splat_device_bytes", C.c_uint64, [C.c_void_p, C.POINTER(C.c_uint64)]),
     ("splat_set_frame_overlap", C.c_int, [C.c_void_p, C.c_int32]),
     ("splat_set_option", C.c_int, [C.c_void_p, C.c_int32, C.c_double]),
@@ -170,6 +171,7 @@ OPT_COUNT_FIRST = 21
 OPT_LARGE_SPLAT_TILES = 22
 OPT_LARGE_LIST_MIN = 23
 OPT_START_REFINE = 24
+OPT_RETAIN_LISTS = 25
 ABI_VERSION = 7          # SPLAT_ABI_VERSION of the header these structures were written against
 
 _LIB = None

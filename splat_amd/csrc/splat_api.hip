@@ -75,6 +75,7 @@ const float* ev_times(const EvSet& s, float t[N_TIMES]) {
     static const int pairs[N_TIMES][2] = {{0, 1}, {1, 2}, {8, 3}, {3, 4}, {5, 6}, {6, 7}};
     for (int k = 0; k < N_TIMES; ++k) {
         t[k] = 0.f;
+        if (s.retained && k < 4) continue;      // (events 0-4 and 8 of this ring entry are an older frame's: a retained frame bins and orders nothing)
         (void)hipEventElapsedTime(&t[k], s.e[pairs[k][0]], s.e[pairs[k][1]]);
     }
     return t;
@@ -164,7 +165,12 @@ static hipError_t copy_to_host_image(uint32_t* dst, const uint32_t* src, size_t 
 // The frame policy's memory speaks of lists that no longer exist (another scene, target, slab, key-buffer layout) or of
 // thresholds that changed (an option): forget it.  Statuses of frames still in the ring stay where they are; ring_kind = 0
 // makes the policy ignore them ('binned twice' words of an earlier scene could arm 64 count-first frames on the next).
+// RETAINED LISTS (include/splat_retain.h): whatever changes what K1, the scan or the ordering of a frame would read or
+// produce ends the retained set -- the next frame's decision sees another epoch.
+void bump_epoch(splat_ctx* c) { ++c->bin_epoch; }
+
 void reset_policy(splat_ctx* c) {
+    bump_epoch(c);
     c->pol.still_frames = 0; c->pol.last_cam_hash = 0;
     c->pol.count_first_left = 0; c->pol.redo_armed = 0;
     std::memset(c->pol.ring_kind, 0, sizeof c->pol.ring_kind);
@@ -221,6 +227,7 @@ int ensure_bins(splat_ctx* c, unsigned int m) {
     int rc = sync_all(c);
     if (rc != SPLAT_OK) return rc;
     c->m_alloc = 0;
+    bump_epoch(c);                         // (the slots' tile tables are made again)
     c->sort_hint = false;                  // another target geometry: the list-length profile is unknown again
     dfree(c->zero_layout);
     HIP_TRY(c, dmalloc(c, &c->zero_layout, sizeof(unsigned int) * (size_t)(m + 1)));
@@ -272,6 +279,7 @@ int ensure_keys(splat_ctx* c, uint64_t want, uint64_t want2) {
     int rc = sync_all(c);
     if (rc != SPLAT_OK) return rc;
     want = std::max(want, c->cap); want2 = std::max(want2, c->cap2);
+    bump_epoch(c);                         // (the slots' key buffers are made again)
     const bool grow1 = want > c->cap, grow2 = want2 > c->cap2;
     // The last frame's lists stay readable (splat_get_tile_lists): a frame whose regions asked for more than the buffer holds
     // was squeezed into it and is complete, and the growth it asked for comes behind it (finish_frame) -- its slot's keys are
@@ -399,6 +407,7 @@ struct FrameLaunch {
     hipStream_t bs, ss, cs;     // binning, ordering, compositor
     TileLists lists;
     KeyBuffers keys;
+    int retain;                 // SPLAT_RETAIN_*: an ordinary frame, the writer of a retained set, a frame composited from that set
     hipError_t mark(int k, hipStream_t st) const { return timed ? hipEventRecord(ev->e[k], st) : hipSuccess; }
 };
 
@@ -453,7 +462,6 @@ int bin_frame(splat_ctx* c, const FrameLaunch& f) {
         HIP_TRY(c, hipMemsetAsync(f.d_st, 0, sizeof(FrameStatus), bs));
     }
     const uint64_t cam_hash = pd.cam_hash;      // (what places the Gaussians on the target: the camera and the slab)
-    c->fc.start_hints = pd.start_hints_mode; c->fc.start_light = pd.start_light; c->fc.early_min = pd.early_min;
     BinArgs k1{};
     k1.s = bs; k1.knobs = &c->knobs; k1.scene = scene_of(c); k1.fc = c->fc;
     k1.recs = s.recs; k1.depth = s.depth; k1.rect = s.rect; k1.vislist = s.vislist; k1.keys = s.keys; k1.blockinfo = s.blockinfo; k1.status = f.d_st;
@@ -614,10 +622,14 @@ int composite_frame(splat_ctx* c, const FrameLaunch& f, uint32_t* d_argb, bool w
     hipStream_t cs = f.cs;
     const unsigned int m = c->n_tiles;
     if (c->pre_wait) { HIP_TRY(c, hipStreamWaitEvent(cs, c->pre_wait, 0)); c->pre_wait = nullptr; }
-    if (c->pipeline && f.ss != cs) {
+    const bool retained = f.retain == SPLAT_RETAIN_RETAIN;      // (nothing in front of this compositor but the compositors before it, on this stream)
+    if (c->pipeline && f.ss != cs && !retained) {
         HIP_TRY(c, hipEventRecord(s.ev_ready, f.ss));
         HIP_TRY(c, hipStreamWaitEvent(cs, s.ev_ready, 0));
     }
+    // A retained frame's status is its own, from the values the writer's scan left: the compositor checks `overflow` and counts
+    // its retries there (one 1-thread launch in front of it; the host copy is filled in enqueue_frame)
+    if (retained) launch_status_set(cs, f.d_st, c->ret_set.status);
     HIP_TRY(c, f.mark(5, cs));
     uint2* iters = nullptr;
     c->iters_valid = false;
@@ -633,7 +645,8 @@ int composite_frame(splat_ctx* c, const FrameLaunch& f, uint32_t* d_argb, bool w
     }
     CompositeArgs comp{};
     comp.s = cs; comp.knobs = &c->knobs; comp.n_tiles = m; comp.fc = c->fc; comp.recs = s.recs; comp.argb = d_argb; comp.status = f.d_st; comp.orig = c->orig;
-    comp.fused_sort_max = c->fused_sort_max; comp.iters = iters; comp.keep_keys = want_iters;
+    // (the writer's workgroups store every list they sort back to its region; a retained frame's read them all from there)
+    comp.fused_sort_max = retained ? 0u : c->fused_sort_max; comp.iters = iters; comp.keep_keys = want_iters || f.retain == SPLAT_RETAIN_WRITER;
     // throughput-bound frames (many pairs per key of the longest list: C3 737, C5 3100) keep the one-record walk, the
     // others (C2 316, an eighth-of-a-frame slab 92, C1 36) take the paired one; measured crossover between 316 and 737
     comp.pair_walk = pd.pair_walk != 0;
@@ -642,10 +655,16 @@ int composite_frame(splat_ctx* c, const FrameLaunch& f, uint32_t* d_argb, bool w
     // orders the long lists itself, the selections' lengths only where launch_select ran
     comp.lists = f.lists; comp.lists.near_m = pd.near_cap ? s.near_m : nullptr;
     comp.keys = f.keys; comp.keys.keys2 = pd.comp_sorts != 0 ? s.keys2 : nullptr;
+    if (retained) {
+        // the long lists as the writer's ordering left them: its selections (near_m, the second key buffer), or in order in
+        // their regions -- by its sort launches or its own workgroups -- which flavour 0 reads
+        const bool near = c->ret_set.near_cap != 0u;
+        comp.lists.near_m = near ? s.near_m : nullptr; comp.keys.keys2 = near ? s.keys2 : nullptr;
+    }
     comp.hints = hint_table(c);
     comp.refine = c->fc.close_width == 0.0f ? pd.refine : 0u;      // (exact modes only: a fast-mode frame depends on where its walks start)
     launch_composite(comp);
-    c->last_near = pd.near_cap != 0u;
+    c->last_near = retained ? c->ret_set.near_cap != 0u : pd.near_cap != 0u;
     HIP_TRY(c, f.mark(6, cs));
     // the scan has already delivered this frame's status to h_status[r]; a statistics frame refreshes it with the late
     // counters (compositor retries, sort fallbacks)
@@ -654,14 +673,56 @@ int composite_frame(splat_ctx* c, const FrameLaunch& f, uint32_t* d_argb, bool w
     return SPLAT_OK;
 }
 
-// Enqueue one frame.  Never blocks the host unless the event ring wraps onto a frame that is
-// still running (32 frames behind).
+// RETAINED LISTS: this frame's decision (splat_retain_decide, include/splat_retain.h) from the camera's bytes, the binning
+// epoch and the writer's status.  The frame behind a writer needs that writer's verdict: where its scan has not delivered
+// it yet (a host that enqueues faster than the device renders), the host waits for the writer ONCE per rest -- the frames
+// in flight drain, and what follows costs a compositor each.
+int decide_retention(splat_ctx* c, const splat_camera* cam, int* action) {
+    splat_retain_input in;
+    std::memset(&in, 0, sizeof in);
+    static_assert(sizeof(splat_camera) + 2 * sizeof(int32_t) <= sizeof in.cam, "the camera and the slab fit the decision's words");
+    std::memcpy(in.cam, cam, sizeof(splat_camera));
+    const int32_t slab[2] = {c->slab0, c->slab1};
+    std::memcpy(reinterpret_cast<unsigned char*>(in.cam) + sizeof(splat_camera), slab, sizeof slab);
+    in.epoch = c->bin_epoch; in.still_frames = c->pol.still_frames;
+    // (a debug launch of the N longest tiles only would leave the other lists unsorted behind a writer)
+    in.enabled = (c->retain_lists != 0 && c->knobs.dbg_ntiles == 0u) ? 1 : 0;
+    in.overlap = c->overlap; in.one_pass = c->fc.bucket_cap ? 1 : 0;
+    splat_retain_decision d;
+    const int wr = c->ret_set.ring;
+    for (int pass = 0; pass < 2; ++pass) {
+        if (c->ret.writer == 1u && wr >= 0) {
+            const volatile FrameStatus* hs = &c->h_status[wr];
+            in.writer_arrived = hs->arrived; in.writer_overflow = hs->overflow; in.writer_redone = hs->redone;
+        }
+        if (splat_retain_decide(&c->ret, &in, &d) != 0) return fail(c, SPLAT_ERR_INVALID, "retention refused its input");
+        // the writer's scan has not reported, and everything else says "retain" (d.wait_for_writer): wait for that frame -- its
+        // ring event, the one event an untimed frame records -- and ask again with its status
+        if (pass == 0 && d.wait_for_writer != 0 && wr >= 0 && c->ring[wr].used) {
+            HIP_TRY(c, hipEventSynchronize(c->ring[wr].e[7]));
+            continue;
+        }
+        break;
+    }
+    if (c->ret.writer == 1u && d.next.writer == 2u) {
+        // established: the set's status is what the writer's scan delivered -- the late counters start from zero in every frame
+        FrameStatus st = c->h_status[wr];
+        st.n_fallback = 0; st.n_sort_fallback = 0; st.n_near_fallback = 0; st.n_probe_fail = 0; st.arrived = 1u;
+        c->ret_set.status = st;
+    }
+    c->ret = d.next;
+    *action = d.action;
+    return SPLAT_OK;
+}
+
+// Enqueue one frame.  Blocks the host only when the event ring wraps onto a frame that is still running (32 frames
+// behind), and once per rest for the writer of a retained set when its status has not arrived yet (decide_retention).
 // `timed`: record the per-kernel timing events.  Every hipEventRecord is a barrier packet that
 // drains its queue for a few microseconds -- nine of them per frame were ~25 us of bubbles in a
 // 590 us frame -- so untimed frames (all but every `timing_every`-th of an asynchronous run) record
 // only the one event that tells the host the frame's status has arrived.
 // The stages: the frame's decisions (splat_policy_decide), bin_frame, order_frame, pick_lane, composite_frame.
-int enqueue_frame(splat_ctx* c, uint32_t* d_argb, bool timed, bool want_iters = false, bool may_overlap = false, bool awaited = false) {
+int enqueue_frame(splat_ctx* c, const splat_camera* cam, uint32_t* d_argb, bool timed, bool want_iters = false, bool may_overlap = false, bool awaited = false) {
     FrameLaunch f{};
     const int r = c->ring_next;
     EvSet& ev = c->ring[r];
@@ -669,9 +730,13 @@ int enqueue_frame(splat_ctx* c, uint32_t* d_argb, bool timed, bool want_iters = 
     c->ring_next = (c->ring_next + 1) % EV_RING;
     harvest(c, r);
     std::memset(&c->h_status[r], 0, sizeof(FrameStatus));      // (this frame's scan fills it; until then it says nothing: see the peek below)
-    const int si = (int)(c->frame_idx++ % (uint64_t)slots_in_use(c));
-    Slot& s = c->slots[si];
-    f.si = si; f.s = &s; f.d_st = c->d_status_ring + r;       // (initialised by this frame's scan)
+    // (slots and binning streams rotate with the frames that are BINNED: after retained frames binning resumes on the slot
+    // behind the writer's, whose regions and cursors the frames before the writer prepared)
+    int si = (int)(c->bin_idx % (uint64_t)slots_in_use(c));
+    const uint64_t bin_no = c->bin_idx + 1;
+    c->frame_idx++;
+    Slot* sp = &c->slots[si];
+    f.d_st = c->d_status_ring + r;       // (initialised by this frame's scan)
     // pipeline depth 1: everything on the caller's stream.  2: K1..K3 of frame N+1 on the bin stream
     // under the compositor of frame N.  3: K1 + scan of frame N+2 on the bin stream, K2 + K3 of
     // frame N+1 on the sort stream, compositor of frame N on the caller's stream -- the bin chain is
@@ -682,15 +747,37 @@ int enqueue_frame(splat_ctx* c, uint32_t* d_argb, bool timed, bool want_iters = 
     // compositor of frame N.  With one chain at a time the frame time IS the chain's length under contention
     // (C3: 0.28 + 0.03 + 0.11 = 0.42 ms against a compositor of 0.37); two in flight leave the compositor as the
     // bound: C3 2241 -> 2334 fps, C1 17.4 k -> 19.2 k, C5 +1 %, C2 -1 %
-    if (c->pipeline >= 6 && (c->frame_idx & 1ull)) f.bs = c->sort_stream;
+    if (c->pipeline >= 6 && (bin_no & 1ull)) f.bs = c->sort_stream;
     f.ss = c->pipeline == 3 ? c->sort_stream : f.bs;     // (4, 5: three / four slots on two streams)
     // THE FRAME'S DECISIONS (include/splat_policy.h): everything below this call only launches what it says.
     {
         const splat_policy_knobs pk = policy_knobs_of(c);
-        const splat_policy_input pi = policy_input_of(c, s, r, awaited);
+        // (the slot the frame would be BINNED into: whether the frame is retained is decided behind the policy, from its still
+        // count.  On a retained frame what the policy says about binning and ordering -- count_first, redo, near_cap,
+        // comp_sorts, the launch sizes -- is not used: composite_frame takes the writer's ordering from ret_set.)
+        const splat_policy_input pi = policy_input_of(c, *sp, r, awaited);
         if (splat_policy_decide(&pk, &c->pol, &pi, &f.pd) != 0) return fail(c, SPLAT_ERR_INVALID, "frame policy refused its input");
         c->pol = f.pd.next;
     }
+    c->fc.start_hints = f.pd.start_hints_mode; c->fc.start_light = f.pd.start_light; c->fc.early_min = f.pd.early_min;
+    // RETAINED LISTS (include/splat_retain.h): bin, bin as the writer, or composite from the writer's slot
+    {
+        int rc = decide_retention(c, cam, &f.retain);
+        if (rc != SPLAT_OK) return rc;
+    }
+    if (f.retain == SPLAT_RETAIN_WRITER) { c->ret_set.slot = si; c->ret_set.ring = r; c->ret_set.near_cap = f.pd.near_cap; }
+    // (the writer carries the per-kernel timing events whatever the sampling says: it is the one frame of a rest whose binning
+    // and ordering exist to be timed -- splat_get_timing over a rest then still knows what a binned frame costs; its semantics
+    // at rest are in include/splat_hip.h)
+    if (f.retain == SPLAT_RETAIN_WRITER) { f.timed = true; timed = true; }
+    if (f.retain == SPLAT_RETAIN_RETAIN) {
+        si = c->ret_set.slot; sp = &c->slots[si];
+        // the frame's status on the host is the writer's (the device copy: composite_frame), and it has arrived
+        c->h_status[r] = c->ret_set.status;
+        c->frames_retained++;
+    } else c->bin_idx++;
+    Slot& s = *sp;
+    f.si = si; f.s = &s;
     // A frame the caller waits for, with nothing else in flight (the reference's loop: one synchronous frame per pose,
     // src/main.rs:69-78), has nothing to overlap with: its whole chain goes on the caller's stream, in order (pd.solo) -- no
     // event recorded on one stream and waited for on another between its binning and its compositor (two barrier packets and
@@ -700,9 +787,12 @@ int enqueue_frame(splat_ctx* c, uint32_t* d_argb, bool timed, bool want_iters = 
     // (two-pass binning: the second buffer mirrors the first)
     f.lists = {s.offsets, s.order, s.lens, s.cursor, c->fc.bucket_cap ? s.off2 : nullptr, s.near_m};
     f.keys = {s.keys, s.keys2, c->cap, (unsigned int)std::min<uint64_t>(c->cap2, 0xffffffffull)};
-    int rc = bin_frame(c, f);
-    if (rc == SPLAT_OK) rc = order_frame(c, f);
-    if (rc != SPLAT_OK) return rc;
+    int rc = SPLAT_OK;
+    if (f.retain != SPLAT_RETAIN_RETAIN) {
+        rc = bin_frame(c, f);
+        if (rc == SPLAT_OK) rc = order_frame(c, f);
+        if (rc != SPLAT_OK) return rc;
+    }
     int li = 0;
     const char* const img_lo = reinterpret_cast<const char*>(d_argb);
     rc = pick_lane(c, img_lo, img_lo + (size_t)c->fc.W * (size_t)c->fc.H * 4u, may_overlap, r, &li);
@@ -715,11 +805,12 @@ int enqueue_frame(splat_ctx* c, uint32_t* d_argb, bool timed, bool want_iters = 
     s.used = true;
     ev.used = true;
     ev.timed = timed;
+    ev.retained = f.retain == SPLAT_RETAIN_RETAIN;
     c->last_ring = r;
     c->last_slot = si;
     c->lane[li].seq = ++c->lane_seq; c->lane[li].ring = r;
     c->last_lane = li;
-    c->last_lists_in_memory = want_iters || c->fused_sort_max == 0;
+    c->last_lists_in_memory = want_iters || c->fused_sort_max == 0 || f.retain != SPLAT_RETAIN_BIN;
     return SPLAT_OK;
 }
 
@@ -749,6 +840,7 @@ int finish_frame(splat_ctx* c, bool* last_skipped = nullptr) {
         // the layout asked for.
         const bool overflowed = c->bucket_overflow;
         c->bucket_overflow = false;
+        bump_epoch(c);
         for (Slot& sl : c->slots) sl.layout_valid = false;
         if (c->layout_want > c->cap) {
             const uint64_t asked = c->layout_want + c->layout_want / 4 + 1024, want = std::min<uint64_t>(asked, KEY_ENTRIES_MAX);
@@ -960,7 +1052,7 @@ bool store_option(splat_ctx* c, int opt, double v, bool dry = false) {
             if (p != c->pipeline) {
                 // another number of frame slots: the key buffers exist per slot in use and are made again by the next frame
                 for (Slot& sl : c->slots) { dfree(sl.keys); dfree(sl.keys2); sl.layout_valid = false; sl.flip = 0; sl.used = false; sl.free_ring = -1; }
-                c->cap = 0; c->cap2 = 0; c->frame_idx = 0;
+                c->cap = 0; c->cap2 = 0; c->frame_idx = 0; c->bin_idx = 0;
                 c->pipeline = p;
                 // One stream for everything has no compositor lanes: the lane state goes as splat_set_frame_overlap(1) leaves it
                 // (unless the operator pinned the overlap from the environment: then only the second lane's stream is dropped, and
@@ -999,6 +1091,7 @@ bool store_option(splat_ctx* c, int opt, double v, bool dry = false) {
         case SPLAT_OPT_LARGE_SPLAT_TILES: if (v < -1.0 || v > 1048576.0 || v != std::floor(v)) return false; SPLAT_DRY_; c->large_tiles = (int)v; return true;
         case SPLAT_OPT_LARGE_LIST_MIN: if (v < -1.0 || v > 1e9 || v != std::floor(v)) return false; SPLAT_DRY_; c->large_list_min = (int)v; return true;
         case SPLAT_OPT_START_REFINE: if (v != 0.0 && v != 1.0) return false; SPLAT_DRY_; c->start_refine = (int)v; return true;
+        case SPLAT_OPT_RETAIN_LISTS: if (v != 0.0 && v != 1.0) return false; SPLAT_DRY_; c->retain_lists = (int)v; return true;
         default: return false;
     }
 #undef SPLAT_DRY_
@@ -1029,6 +1122,7 @@ bool load_option(const splat_ctx* c, int opt, double* v) {
         case SPLAT_OPT_LARGE_SPLAT_TILES: *v = c->large_tiles; return true;
         case SPLAT_OPT_LARGE_LIST_MIN: *v = c->large_list_min; return true;
         case SPLAT_OPT_START_REFINE: *v = c->start_refine; return true;
+        case SPLAT_OPT_RETAIN_LISTS: *v = c->retain_lists; return true;
         default: return false;
     }
 }
@@ -1118,6 +1212,7 @@ int splat_create(const splat_config* cfg, splat_ctx** out) {
     option_from_env(c, SPLAT_OPT_LARGE_SPLAT_TILES, "SPLAT_LARGE_TILES", -1, 1048576);
     option_from_env(c, SPLAT_OPT_LARGE_LIST_MIN, "SPLAT_LARGE_LIST_MIN", -1, 1e9);
     option_from_env(c, SPLAT_OPT_START_REFINE, "SPLAT_START_REFINE", 0, 1);
+    option_from_env(c, SPLAT_OPT_RETAIN_LISTS, "SPLAT_RETAIN", 0, 1);
     if (const char* lm = std::getenv("SPLAT_LAYOUT_MOTION")) c->layout_motion = std::atoi(lm) != 0 ? 1 : 0;
     if (const char* k1 = std::getenv("SPLAT_SORT_RADIX_MIN")) c->knobs.sort_radix_min = (unsigned int)std::max(0, std::atoi(k1));
     if (const char* k2 = std::getenv("SPLAT_SCAN_THREADS")) c->knobs.scan_threads = std::atoi(k2);
@@ -1127,6 +1222,7 @@ int splat_create(const splat_config* cfg, splat_ctx** out) {
     if (const char* k7 = std::getenv("SPLAT_DBG_ONE_PASS_SELECT")) c->one_pass_select = std::atoi(k7) != 0;
     if (const char* k11 = std::getenv("SPLAT_DBG_KEYS2_ENTRIES")) c->knobs.dbg_keys2_entries = std::strtoull(k11, nullptr, 10);
     if (const char* k9 = std::getenv("SPLAT_DBG_HINT_RADIUS")) c->knobs.dbg_hint_radius = std::atoi(k9);
+    if (const char* k12 = std::getenv("SPLAT_DBG_SELECT_BLIND")) c->knobs.dbg_select_blind = std::atoi(k12) != 0 ? 1u : 0u;
     if (const char* k5 = std::getenv("SPLAT_DBG_STARTS")) c->knobs.dbg_starts = std::atoi(k5) != 0 ? 1u : 0u;
     if (const char* k4 = std::getenv("SPLAT_COMP_LDS_PAD")) c->knobs.comp_lds_pad = (unsigned int)std::max(0, std::atoi(k4));
     if (const char* k1p = std::getenv("SPLAT_K1_LDS_PAD")) c->knobs.k1_lds_pad = (unsigned int)std::min(48 * 1024, std::max(0, std::atoi(k1p)));
@@ -1218,6 +1314,7 @@ int splat_set_frame_overlap(splat_ctx* c, int32_t n) {
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     int rc = finish_quiet(c);
     if (rc != SPLAT_OK) return rc;
+    bump_epoch(c);
     c->overlap = n;
     if (n >= 2) return ensure_lane(c);
     c->comp2 = nullptr;                    // (the stream stays: it is the copy stream)
@@ -1237,7 +1334,8 @@ int splat_set_option(splat_ctx* c, int32_t option, double value) {
     if (option == SPLAT_OPT_FRAME_OVERLAP ? (value != 1.0 && value != 2.0) : !store_option(c, option, value, true))
         return fail(c, SPLAT_ERR_INVALID, "option value out of range");
     if (c->env_pinned & (1u << option)) return SPLAT_OK;      // the operator's environment variable stays in force
-    reset_policy(c);      // (the next frames scan for their walks' starts again, nothing stays armed: thresholds may have changed)
+    reset_policy(c);      // (the next frames scan for their walks' starts again, nothing stays armed: thresholds may have changed;
+                          // and a retained set ends -- reset_policy bumps the binning epoch -- whichever option it is: none is exempt)
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     int rc = finish_quiet(c);
     if (rc != SPLAT_OK) return rc;
@@ -1282,6 +1380,7 @@ int splat_set_stream(splat_ctx* c, void* stream) {
 namespace splat {
 // The scene is being replaced: its frames end, and nothing of them is left to redo or to report.
 int end_frames_for_upload(splat_ctx* c) {
+    bump_epoch(c);
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     (void)finish_frame(c);          // (frames of the scene being replaced: nothing left to redo)
     c->deferred_drop = false; c->frames_drop_reported = c->frames_dropped;
@@ -1290,6 +1389,7 @@ int end_frames_for_upload(splat_ctx* c) {
 // The scene is being edited in place: the frames in flight end as above -- they show the scene as it was -- but a frame found
 // skipped stays pending for the next splat_sync, as for every call that quiesces on its way to something else.
 int end_frames_for_edit(splat_ctx* c) {
+    bump_epoch(c);
     HIP_TRY(c, hipSetDevice(c->cfg.device));
     int rc = finish_quiet(c);
     if (rc != SPLAT_OK) return rc;
@@ -1328,6 +1428,7 @@ int splat_set_slab(splat_ctx* c, int32_t tile_row0, int32_t tile_row1) {
     if (!c) return SPLAT_ERR_INVALID;
     if (tile_row0 < 0 || (tile_row1 >= 0 && tile_row1 < tile_row0)) return fail(c, SPLAT_ERR_INVALID, "bad slab");
     if (tile_row0 == c->slab0 && tile_row1 == c->slab1) return SPLAT_OK;
+    bump_epoch(c);
     // another slab: the slots' region layouts (sized from the lists of the OLD slab's tile rows -- a partition that keeps
     // the tile count would keep them otherwise) and the sort launch sizes describe other tiles.  The next frame counts its
     // pairs first (bootstrap) instead of being binned against them, overflowing and getting dropped on the device.
@@ -1365,6 +1466,7 @@ int splat_tile_row_loads(splat_ctx* c, const splat_camera* cam, uint64_t* row_pa
     Slot& s = c->slots[0];
     rc = ensure_two_pass_buffers(c, s);
     if (rc != SPLAT_OK) return rc;
+    bump_epoch(c);              // (the pass below writes the slot's records, tile table and counters)
     fc.bucket_cap = 0;          // count only
     HIP_TRY(c, hipMemsetAsync(s.counts, 0, sizeof(unsigned int) * ((size_t)nt + 1), c->stream));   // (one-pass frames leave cursors there)
     s.layout_valid = false; s.flip = 0;                                                          // ... and will find them gone
@@ -1424,7 +1526,7 @@ int render_device_impl(splat_ctx* c, const splat_camera* cam, void* d_argb, int3
         if (rc != SPLAT_OK) return rc;
         const bool timed = stats != nullptr || c->timing_every <= 1 || (c->frame_idx % (uint64_t)c->timing_every) == 0;
         c->clear_first = clear_first;
-        rc = enqueue_frame(c, (uint32_t*)d_argb, timed, stats != nullptr, !sync && !stats && c->comp2 != nullptr && c->overlap >= 2 && !c->streamed_call,
+        rc = enqueue_frame(c, cam, (uint32_t*)d_argb, timed, stats != nullptr, !sync && !stats && c->comp2 != nullptr && c->overlap >= 2 && !c->streamed_call,
                            sync || stats != nullptr);
         c->clear_first = false;
         if (rc != SPLAT_OK) return rc;
@@ -1666,6 +1768,12 @@ int splat_sync(splat_ctx* c) {
 
 uint64_t splat_frames_dropped(const splat_ctx* c) { return c ? c->frames_dropped : 0; }
 
+int splat_frames_retained(splat_ctx* c, uint64_t* n) {
+    if (!c || !n) return SPLAT_ERR_INVALID;
+    *n = c->frames_retained;
+    return SPLAT_OK;
+}
+
 uint64_t splat_device_bytes(const splat_ctx* c, uint64_t* peak) {
     if (!c) return 0;
     if (peak) *peak = c->dev_bytes_peak;
@@ -1700,6 +1808,7 @@ int splat_get_records(splat_ctx* c, splat_record* out, uint64_t n) {
         // Depth and pixel rectangle exist only in registers on the one-pass path, and block culling skips whole
         // blocks (whose records above are then stale, for Gaussians that reach nothing): recompute those two with
         // the counting flavour of K1, culling off (same code, same values), then clear its counts again.
+        bump_epoch(c);          // (the pass below writes the slot's records and counters)
         FrameConst fc = c->fc;
         fc.bucket_cap = 0; fc.cull_blocks = 0;
         Slot& sl = c->slots[c->last_slot];
@@ -1779,6 +1888,7 @@ int splat_get_tile_lists(splat_ctx* c, uint32_t* tile_offsets, uint64_t n_offset
     if (c->last_near && c->last.overflow == 0) {
         // the frame's compositor selected the nearest keys of every list of more than 2048 keys and left the list itself
         // as K1 had written it: put those lists in order now (the sort launches, every tile in their grids)
+        bump_epoch(c);          // (the selections a retained frame would read are scatter space of these sorts)
         SortArgs sort{};
         sort.s = c->stream; sort.knobs = &c->knobs; sort.n_tiles = c->n_tiles; sort.grids = {c->n_tiles, c->n_tiles, c->n_tiles};
         sort.lists = {s.offsets, s.order, s.lens, s.cursor, c->fc.bucket_cap ? s.off2 : nullptr, s.near_m};

@@ -9,6 +9,7 @@
 
 #include "splat_internal.h"
 #include "../../include/splat_policy.h"
+#include "../../include/splat_retain.h"
 
 #define HIP_TRY(ctx, expr)                                                                             \
     do {                                                                                               \
@@ -30,6 +31,7 @@ struct EvSet {
     hipEvent_t e[N_EV];
     bool used = false;
     bool timed = false;        // the per-kernel events e0..e6, e8 were recorded for this frame
+    bool retained = false;     // ... of which a retained frame (splat_retain.h) records e5, e6 only: the others are an older frame's
 };
 
 struct Slot {                  // everything one frame writes before the image
@@ -152,6 +154,19 @@ struct splat_ctx {
     splat::LaunchKnobs knobs;              // experiment switches of the launch wrappers (this context's)
     float region_spare = 4.0f;             // SPLAT_REGION_SPARE: how far a tile's region may grow into the key buffer's spare room (1: not at all)
     uint64_t frame_idx = 0;
+    uint64_t bin_idx = 0;                  // frames BINNED so far: slots and binning streams rotate with these (a retained frame bins nothing)
+    // Retained lists (include/splat_retain.h; enqueue_frame): with the camera at rest one frame -- the WRITER -- leaves every
+    // list it composited from in order in memory (the compositor's write-back), and the frames behind it composite from its
+    // slot alone until the camera's bytes or the binning epoch change.
+    int retain_lists = 1;                  // SPLAT_OPT_RETAIN_LISTS / SPLAT_RETAIN
+    uint64_t bin_epoch = 0;                // bumped wherever something a frame's binning or ordering reads or produces changes (bump_epoch)
+    splat_retain_state ret{};
+    uint64_t frames_retained = 0;
+    struct RetainSet {                     // the writer: its slot and ring entry, how its long lists were ordered, its status as the scan left it
+        int slot = -1, ring = -1;
+        unsigned int near_cap = 0;
+        splat::FrameStatus status{};
+    } ret_set;
     int last_slot = -1;                    // buffer slot of the most recent frame (debug getters)
     bool last_lists_in_memory = false;     // ... and whether its compositor wrote the lists it sorted back to the buckets
     splat::FrameStatus* h_status = nullptr;  // pinned, one per event-ring entry

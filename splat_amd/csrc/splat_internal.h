@@ -116,6 +116,8 @@ struct LaunchKnobs {
     unsigned int dbg_select_stride = 0;    // SPLAT_DBG_SELECT_STRIDE: slots of the tile order per workgroup of the near selection's launch (default 8)
     unsigned long long dbg_keys2_entries = 0; // SPLAT_DBG_KEYS2_ENTRIES: initial size of a frame slot's second key buffer (tests force its growth)
     int dbg_hint_radius = -1;              // SPLAT_DBG_HINT_RADIUS: the near selection's neighbourhood, in tiles (default: by the camera's motion)
+    unsigned int dbg_select_blind = 0;     // SPLAT_DBG_SELECT_BLIND: the near selection ignores what the walks needed last frame (every selection is
+                                           // near_cap keys: with a small near_cap the long tiles repair themselves on every binned frame -- tests)
     unsigned int dbg_starts = 0;           // SPLAT_DBG_STARTS: statistics frames record (list length, nearest keys the walk needed) per wave
 };
 
@@ -321,6 +323,8 @@ struct CompositeArgs {
     unsigned int refine;            // != 0: this frame's waves refine their starts (splat_policy_decision::refine)
 };
 void launch_composite(const CompositeArgs& a);
+// a frame composited from retained lists: its device status starts from these values (no scan ran to initialise it)
+void launch_status_set(hipStream_t s, FrameStatus* status, const FrameStatus& v);
 hipError_t init_device_kernels();   // per-device kernel attributes; call with the device current
 
 // ---- splat_multi.hip: the multi-GPU layer's hooks into a context (splat_ctx itself stays private to the host files that

@@ -3355,6 +3355,13 @@ static __device__ __attribute__((noinline)) void repair_tile(KernArgs ka, unsign
     }
     composite_tile<PAIR, LIBM, 1>(smem, exptab, it, fc, k->offsets, k->order, k->lens, k->keys, k->recs, k->argb, k->status, k->fused_sort_max, k->radix_min,
                                   k->iters, k->keep_keys, k->orig, k->clear_first, k->keys2, nullptr, k->need_hint, k->start_hint, k->off2, k, again, true);
+    // The list is now in order in its region, and the tile's room in the second key buffer -- where its selection lay -- was
+    // the sort's scratch: say so, for whoever reads this slot's lists again (a frame composited from retained lists:
+    // splat_retain.h).  Nobody else reads this word within the frame: only this workgroup has this tile.
+    if (threadIdx.x == 0u) {
+        const unsigned int tile = k->order[it];
+        const_cast<unsigned int*>(k->near_m)[tile] = k->lens[tile];
+    }
 }
 
 // NEAR SELECTION, the kernel (one workgroup per slot of the longest-first tile order; 256 threads and the compositor's
@@ -3376,7 +3383,7 @@ __global__ __launch_bounds__(256) void select_near_kernel(const unsigned int* __
                                                           const unsigned int* __restrict__ need_hint, unsigned int* __restrict__ near_m,
                                                           unsigned int tiles_x, unsigned int tile_rows, unsigned int* __restrict__ near_thr,
                                                           unsigned int n_slots, unsigned int at_rest, const unsigned int* __restrict__ off2,
-                                                          int hint_radius) {
+                                                          int hint_radius, unsigned int blind) {
     __shared__ __attribute__((aligned(16))) unsigned char smem[sort_lds_bytes<256, 2048>()];
     if (status->overflow) return;
     // (an eighth as many workgroups as tiles, each taking the slots blockIdx.x, + gridDim.x, ... of the longest-first order until it
@@ -3425,6 +3432,7 @@ __global__ __launch_bounds__(256) void select_near_kernel(const unsigned int* __
         __syncthreads();
         deepest = (unsigned int)__builtin_amdgcn_readfirstlane((int)word[0]);
         thr = (unsigned int)__builtin_amdgcn_readfirstlane((int)word[1]);
+        if (blind) { deepest = 0u; thr = 0u; }      // (debug: nothing known about the walks' needs, on every frame -- tiles keep repairing)
         __syncthreads();                    // (the workspace is the selection's from here on)
         // (While the hint leaves room, the selection is the full workspace: this kernel runs beside the previous frame's
         // compositor, its time is hidden, and a moving camera puts other Gaussians under the tile than the hint saw -- a
@@ -3477,6 +3485,13 @@ __global__ __launch_bounds__(256) void select_near_kernel(const unsigned int* __
     }
     __syncthreads();                            // the workspace is the next slot's
   }
+}
+
+// A frame composited from retained lists (splat_retain.h) has no scan to initialise its status: one thread stores the values
+// the writer's scan left (passed by value: no buffer to keep them in).
+__global__ void status_set_kernel(FrameStatus* __restrict__ status, const FrameStatus v) { *status = v; }
+void launch_status_set(hipStream_t s, FrameStatus* status, const FrameStatus& v) {
+    hipLaunchKernelGGL(status_set_kernel, dim3(1), dim3(1), 0, s, status, v);
 }
 
 // The launch: one workgroup per tile, slot blockIdx.x of the longest-first order.  (A persistent grid pulling
@@ -3679,7 +3694,7 @@ void launch_select(const SelectArgs& a) {
     if (a.knobs->dbg_select_stride) grid = (n_tiles + a.knobs->dbg_select_stride - 1u) / a.knobs->dbg_select_stride;
     if (!grid) grid = (n_tiles + 7u) / 8u;
     hipLaunchKernelGGL(select_near_kernel, dim3(std::min(grid, n_tiles)), dim3(256), 0, a.s, a.lists.offsets, a.lists.order, a.lists.lens, a.keys.keys, a.keys.keys2, a.status, a.orig, a.knobs->sort_radix_min,
-                       std::min(std::max(a.near_cap, 64u), 2048u), a.need_hint, a.lists.near_m, a.tiles_x, a.tile_rows, a.near_thr, n_tiles, a.at_rest ? 1u : 0u, off2, std::min(std::max(hint_radius, 0), 7));
+                       std::min(std::max(a.near_cap, 64u), 2048u), a.need_hint, a.lists.near_m, a.tiles_x, a.tile_rows, a.near_thr, n_tiles, a.at_rest ? 1u : 0u, off2, std::min(std::max(hint_radius, 0), 7), a.knobs->dbg_select_blind);
 }
 void launch_composite(const CompositeArgs& c) {
     unsigned int n_tiles = c.n_tiles;

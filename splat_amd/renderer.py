@@ -484,6 +484,13 @@ class Renderer:
         """frames skipped on the device since the context was created (redone internally or reported)"""
         return int(self._L.splat_frames_dropped(self._h))
 
+    def frames_retained(self):
+        """frames since the context was created that were composited from retained lists (OPT_RETAIN_LISTS): the compositor
+        alone, on the lists an earlier frame of the same camera left in order"""
+        n = C.c_uint64()
+        self._check(self._L.splat_frames_retained(self._h, C.byref(n)))
+        return int(n.value)
+
     # ---- viewer-loop streaming (src/main.rs:69-78): cleared frame -> async copy into a host buffer
     @staticmethod
     def host_register(arr):
