@@ -41,7 +41,8 @@ extern "C" {
  * splat_upload_ply_device (and the splat_ply_layout they take).  A library of version 7 may predate them: a binding
  * that wants them finds them by symbol (dlsym / hasattr) and does without them where they are missing.  Likewise
  * splat_update_scene_device and splat_update_gaussians_device (and the SPLAT_FIELD_* bits they take), and
- * splat_select_device and splat_selection_indices_device (and the splat_select_query and SPLAT_SEL_* values they take). */
+ * splat_select_device and splat_selection_indices_device (and the splat_select_query and SPLAT_SEL_* values they take), and
+ * splat_read_scene_device, splat_read_gaussians_device, splat_transform_scene_device and splat_transform_gaussians_device. */
 
 /* modes: bit flags, 0 = the default */
 #define SPLAT_MODE_EXACT 0       /* back-to-front, 8-bit truncation per splat as blend() does it; the exponential of
@@ -265,6 +266,55 @@ int splat_select_device(splat_ctx* ctx, const splat_select_query* q, const splat
  * d_index_out with n > 0 and capacity > 0. */
 int splat_selection_indices_device(splat_ctx* ctx, uint64_t n, const void* d_selection, void* d_index_out,
                                    uint64_t capacity, uint64_t* count_out, void* producer_stream);
+
+/* The resident values GIVEN BACK, and changed WHERE THEY LIE: with these two an editor that moves, rotates or scales a
+ * selection keeps no copy of the scene (after an upload from PLY rows it never had one), and select -> indices -> transform,
+ * or -> read -> anything -> update, stays on the GPU.  The scene holds the floats of its uploads and edits losslessly, so a
+ * read returns them bit for bit.
+ * splat_read_scene_device is the inverse of splat_update_scene_device: the named fields (SPLAT_FIELD_* bits) of all n
+ * Gaussians into the caller's device buffers, in the updates' layouts, rows in ORIGINAL index order.  pos4 gets x y z and
+ * w = 1.0f (the scene does not store w; the uploads never read it).  A buffer whose field is not named is left untouched
+ * and may be NULL.
+ * splat_read_gaussians_device is the inverse of splat_update_gaussians_device: COMPACT rows, row t = Gaussian d_index[t]
+ * (u32 original indices; producer_stream as for splat_upload_scene_device: the stream that wrote them).  Duplicate indices
+ * are fine: each output row is written on its own.  An index >= n: SPLAT_ERR_INVALID and nothing is written (the indices
+ * are checked on the device first).
+ * Both READ the scene as splat_select_device does: synchronous, ordered on the context's stream behind the frames in
+ * flight, and the state kept from frame to frame (tile regions, hints, the frame policy, retained lists) survives.
+ * splat_device_bytes() is as before, except that the first indexed read of a scene makes the inverse of the order as the
+ * first splat_update_gaussians_device does (4 bytes per Gaussian and one byte per block, kept until the scene is replaced),
+ * unless an indexed edit has made it already.
+ * SPLAT_ERR_INVALID, before any device work, as for the updates: a NULL context, unknown bits in `fields`, a named field's
+ * pointer NULL with n or k > 0, k > 0 with a NULL d_index, k > n (kept for symmetry: the rows are meant to be usable as an
+ * update); SPLAT_ERR_NO_SCENE: no resident scene; SPLAT_ERR_INVALID: n is not the resident scene's.  fields == 0 or
+ * k == 0: SPLAT_OK, nothing done. */
+int splat_read_scene_device(splat_ctx* ctx, uint64_t n, uint32_t fields, void* d_pos4, void* d_cov3d, void* d_opacity,
+                            void* d_sh);
+int splat_read_gaussians_device(splat_ctx* ctx, uint64_t k, const void* d_index, uint32_t fields, void* d_pos4,
+                                void* d_cov3d, void* d_opacity, void* d_sh, void* producer_stream);
+/* An affine map applied to the positions and 3D covariances of the whole scene, or of the k Gaussians d_index[0..k), in
+ * place.  m: 3x4 row-major in HOST memory, world -> world, the layout of splat_select_query.world_to_unit.  With
+ * A(r,k) = m[4r+k] and S(r,c) = cov[3c+r] (the blocks are column-major), every product and every sum rounded to f32 once,
+ * unfused, in exactly this order:
+ *   p'_r    = ((A(r,0) x + A(r,1) y) + A(r,2) z) + m[4r+3]
+ *   T(r,c)  =  (A(r,0) S(0,c) + A(r,1) S(1,c)) + A(r,2) S(2,c)
+ *   S'(r,c) =  (T(r,0) A(c,0) + T(r,1) A(c,1)) + T(r,2) A(c,2)        all nine, each on its own
+ * which is S' = A S A^T.  Nothing is symmetrised; with the identity the values come back equal (a -0 may become +0).  Any
+ * float in m is accepted; nothing checks it.  Opacity and sh keep their bits.  sh is NOT rotated: view-dependent colour
+ * keeps its world-space lobes -- a caller that wants it turned reads sh, rotates it and updates it.
+ * A transform is an EDIT and behaves as splat_update_* does: synchronous, the frames in flight complete first and show the
+ * scene as it was, the K1 block bounds are recomputed from the resident values (of all blocks, or of those that hold a
+ * mapped Gaussian), the state kept from frame to frame starts over; the frames that follow are those of a fresh
+ * splat_upload_scene of the mapped arrays, byte for byte.  The indexed form checks the indices on the device before anything
+ * is written (an index >= n: SPLAT_ERR_INVALID, nothing applied) and makes the inverse order like the other indexed calls.
+ * Duplicate indices are the caller's error: such a Gaussian may be mapped once or twice; nothing faults.
+ * SPLAT_ERR_INVALID, before any device work: a NULL context or m, k > 0 with a NULL d_index, k > n; SPLAT_ERR_NO_SCENE: no
+ * resident scene.  k == 0: SPLAT_OK, nothing done.
+ * The multi-GPU layer (splat_multi_*) has no counterpart, as for the updates: read from one rank's context, transform each
+ * rank's (splat_multi_ctx). */
+int splat_transform_scene_device(splat_ctx* ctx, const float m[12]);
+int splat_transform_gaussians_device(splat_ctx* ctx, uint64_t k, const void* d_index, const float m[12],
+                                     void* producer_stream);
 
 /* Debug / stage parity: the stored scene order and K1 block bounds of the current scene.
  * orig_out: n u32 (slot j holds original Gaussian orig[j]); bounds_out: ceil(n/256) x 8 f32

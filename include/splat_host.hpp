@@ -91,6 +91,16 @@ void update_scene_device(splat_ctx* ctx, uint64_t n, uint32_t fields, const void
                          const void* d_opacity, const void* d_sh, void* producer_stream = nullptr);
 void update_gaussians_device(splat_ctx* ctx, uint64_t k, const void* d_index, uint32_t fields, const void* d_pos4,
                              const void* d_cov3d, const void* d_opacity, const void* d_sh, void* producer_stream = nullptr);
+// ... read back into DEVICE buffers (splat_read_scene_device, splat_read_gaussians_device: the inverses of the two above, same
+// layouts, pos4's w = 1, a buffer whose field is not named stays untouched and may be null; duplicate indices are fine), and
+// mapped where it lies (splat_transform_scene_device, splat_transform_gaussians_device): m = 3x4 row-major affine map in host
+// memory, applied to positions and 3D covariances (A S A^T); opacity and sh keep their bits, sh is not rotated.  The reads
+// leave the state kept from frame to frame alone; a transform is an edit like the updates.  Throw what the C calls refuse.
+void read_scene_device(splat_ctx* ctx, uint64_t n, uint32_t fields, void* d_pos4, void* d_cov3d, void* d_opacity, void* d_sh);
+void read_gaussians_device(splat_ctx* ctx, uint64_t k, const void* d_index, uint32_t fields, void* d_pos4, void* d_cov3d,
+                           void* d_opacity, void* d_sh, void* producer_stream = nullptr);
+void transform_scene_device(splat_ctx* ctx, const float m[12]);
+void transform_gaussians_device(splat_ctx* ctx, uint64_t k, const void* d_index, const float m[12], void* producer_stream = nullptr);
 
 struct GaussianList {           // src/gaussians.rs:408-416, SoA
     std::vector<float> positions;   // 4 x N (x,y,z,1)

@@ -150,6 +150,18 @@ extern "C" {
     // ... and its indices, ascending, as u32: a d_index for splat_update_gaussians_device; *count_out may exceed capacity
     pub fn splat_selection_indices_device(ctx: *mut SplatCtx, n: u64, d_selection: *const c_void, d_index_out: *mut c_void,
                                           capacity: u64, count_out: *mut u64, producer_stream: *mut c_void) -> c_int;
+    // the resident values given back, and mapped where they lie (added under ABI 7, found by symbol like those above): the reads
+    // are the updates' inverses (same layouts and SPLAT_FIELD_* bits; pos4 gets w = 1; a buffer whose field is not named may be
+    // null and is left untouched) and read the scene as a selection does; m = 3x4 row-major affine map in HOST memory, applied
+    // to positions and 3D covariances (A S A^T) in place -- an edit like the updates; sh is not rotated
+    pub fn splat_read_scene_device(ctx: *mut SplatCtx, n: u64, fields: u32, d_pos4: *mut c_void, d_cov3d: *mut c_void,
+                                   d_opacity: *mut c_void, d_sh: *mut c_void) -> c_int;
+    pub fn splat_read_gaussians_device(ctx: *mut SplatCtx, k: u64, d_index: *const c_void, fields: u32, d_pos4: *mut c_void,
+                                       d_cov3d: *mut c_void, d_opacity: *mut c_void, d_sh: *mut c_void,
+                                       producer_stream: *mut c_void) -> c_int;
+    pub fn splat_transform_scene_device(ctx: *mut SplatCtx, m: *const f32) -> c_int;
+    pub fn splat_transform_gaussians_device(ctx: *mut SplatCtx, k: u64, d_index: *const c_void, m: *const f32,
+                                            producer_stream: *mut c_void) -> c_int;
     // debug / stage parity: the stored order (n u32) and the K1 block bounds (ceil(n/256) x 8 f32); either may be null
     pub fn splat_get_scene_layout(ctx: *mut SplatCtx, orig_out: *mut u32, n: u64, bounds_out: *mut f32, n_blocks: u64) -> c_int;
     pub fn splat_set_slab(ctx: *mut SplatCtx, tile_row0: i32, tile_row1: i32) -> c_int;

@@ -41,7 +41,7 @@ class Record(C.Structure):
                 ("px0", C.c_int32), ("px1", C.c_int32), ("py0", C.c_int32), ("py1", C.c_int32)]
 
 
-# SPLAT_FIELD_*: the fields an in-place edit names (splat_update_scene_device, splat_update_gaussians_device)
+# SPLAT_FIELD_*: the fields an in-place edit or a read names (splat_update_*_device, splat_read_*_device)
 FIELD_POS, FIELD_COV3D, FIELD_OPACITY, FIELD_SH = 1, 2, 4, 8
 
 # SPLAT_SEL_*: the tests a selection query names, and how its result combines with the selection (splat_select_device)
@@ -92,6 +92,11 @@ SYMBOLS = [
                                       C.POINTER(C.c_uint64), C.c_void_p]),
     ("splat_selection_indices_device", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
                                                  C.c_void_p]),
+    ("splat_read_scene_device", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("splat_read_gaussians_device", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]),
+    ("splat_transform_scene_device", C.c_int, [C.c_void_p, _fp]),
+    ("splat_transform_gaussians_device", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, _fp, C.c_void_p]),
     ("splat_get_scene_layout", C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint64, _fp, C.c_uint64]),
     ("splat_set_slab", C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     ("splat_tile_row_loads", C.c_int, [C.c_void_p, C.POINTER(CameraC), C.POINTER(C.c_uint64), C.c_int32]),

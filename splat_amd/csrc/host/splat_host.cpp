@@ -352,6 +352,28 @@ void update_gaussians_device(splat_ctx* ctx, uint64_t k, const void* d_index, ui
           "splat_update_gaussians_device");
 }
 
+void read_scene_device(splat_ctx* ctx, uint64_t n, uint32_t fields, void* d_pos4, void* d_cov3d, void* d_opacity, void* d_sh) {
+    if (!ctx) throw std::runtime_error("read_scene_device: no context");
+    check(splat_read_scene_device(ctx, n, fields, d_pos4, d_cov3d, d_opacity, d_sh), ctx, "splat_read_scene_device");
+}
+
+void read_gaussians_device(splat_ctx* ctx, uint64_t k, const void* d_index, uint32_t fields, void* d_pos4, void* d_cov3d,
+                           void* d_opacity, void* d_sh, void* producer_stream) {
+    if (!ctx) throw std::runtime_error("read_gaussians_device: no context");
+    check(splat_read_gaussians_device(ctx, k, d_index, fields, d_pos4, d_cov3d, d_opacity, d_sh, producer_stream), ctx,
+          "splat_read_gaussians_device");
+}
+
+void transform_scene_device(splat_ctx* ctx, const float m[12]) {
+    if (!ctx) throw std::runtime_error("transform_scene_device: no context");
+    check(splat_transform_scene_device(ctx, m), ctx, "splat_transform_scene_device");
+}
+
+void transform_gaussians_device(splat_ctx* ctx, uint64_t k, const void* d_index, const float m[12], void* producer_stream) {
+    if (!ctx) throw std::runtime_error("transform_gaussians_device: no context");
+    check(splat_transform_gaussians_device(ctx, k, d_index, m, producer_stream), ctx, "splat_transform_gaussians_device");
+}
+
 // load_from_ply (src/gaussians.rs:375-405): the AoS `Vec<Gaussian>` the reference returns, from the same decode
 std::vector<Gaussian> load_from_ply(const std::string& filename) {
     GaussianList l = load_from_ply_soa(filename, 0);

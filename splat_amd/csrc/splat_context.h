@@ -127,7 +127,7 @@ struct splat_ctx {
     splat::BlockBounds* bounds = nullptr;  // per K1 block of 256 slots (block culling)
     bool cull_blocks = true;               // SPLAT_CULL=0 disables
     std::vector<unsigned int> h_orig;      // host copy of orig (ensure_h_orig: a device upload leaves it empty until a debug getter asks)
-    // in-place edits by index (splat_update_gaussians_device): ONE allocation, made by the first such call on a scene and
+    // edits, transforms and reads by index (splat_*_gaussians_device): ONE allocation, made by the first such call on a scene and
     // freed with it -- inv[i] = the slot of Gaussian i (n words), the index check's counter, one dirty byte per K1 block
     unsigned int* inv = nullptr;
     unsigned int* upd_bad = nullptr;       // (inside inv's allocation)

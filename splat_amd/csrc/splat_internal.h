@@ -175,6 +175,18 @@ void launch_repack_indexed(hipStream_t s, uint64_t n, uint64_t k, const unsigned
 // ... and the bounds of the K1 blocks from the planes, as block_bounds computes them from the buffers; dirty != nullptr:
 // only the blocks whose byte is set, which is cleared
 void launch_plane_bounds(hipStream_t s, uint64_t n, const float4* planes, unsigned char* dirty, BlockBounds* bounds);
+// ... read back and mapped in place (splat_transform.hip).  The unpacks are the repacks run backwards: the whole-scene form
+// writes row orig[j] from slot j, the indexed form row t of the compact buffers from slot inv[index[t]]; pos4's w comes
+// back as 1; a buffer whose field is not named is not written.  The transforms apply the 3x4 row-major affine map m to the
+// centre and the covariance (splat_transform_math.h) of every slot, or of the slots inv[index[t]], whose blocks are marked
+// in `dirty` (required).  The indices arrive checked (launch_index_check).
+void launch_unpack_scene(hipStream_t s, uint64_t n, uint32_t fields, float* pos4, float* cov3d, float* opacity, float* sh,
+                         const unsigned int* orig, const float4* planes);
+void launch_unpack_indexed(hipStream_t s, uint64_t n, uint64_t k, const unsigned int* index, uint32_t fields, float* pos4,
+                           float* cov3d, float* opacity, float* sh, const unsigned int* inv, const float4* planes);
+void launch_transform_scene(hipStream_t s, uint64_t n, const float m[12], float4* planes);
+void launch_transform_indexed(hipStream_t s, uint64_t n, uint64_t k, const unsigned int* index, const float m[12],
+                              const unsigned int* inv, float4* planes, unsigned char* dirty);
 
 // A selection made from the resident scene (splat_select.hip).  SelectView: the camera and conventions the vertex stage's
 // geometry half needs -- a frame's, without slab, binning or compositor state.  The query arrives checked, its rectangle

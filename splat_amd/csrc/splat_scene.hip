@@ -1,7 +1,7 @@
 // splat_scene.hip -- everything that puts values into the resident scene: the uploads (host buffers, device buffers, PLY
 // rows), the in-place edits, K0 (cov3d) and the scene's layout read back -- and the selections read from it, which name the
 // Gaussians such an edit is for.  Host side only, no device code: the kernels are splat_kernels.hip's (order, bounds,
-// packing), splat_ply.hip's, splat_update.hip's and splat_select.hip's.  What the frame scheduler
+// packing), splat_ply.hip's, splat_update.hip's, splat_transform.hip's and splat_select.hip's.  What the frame scheduler
 // (splat_api.hip) holds per scene is behind the seam of splat_context.h.
 #include <algorithm>
 #include <cmath>
@@ -171,6 +171,15 @@ hipError_t ensure_inverse(splat_ctx* c) {
     if (e != hipSuccess) { dfree(c->inv); c->upd_bad = nullptr; c->upd_dirty = nullptr; return e; }
     launch_inverse_order(c->stream, n, c->orig, c->inv);
     return hipGetLastError();
+}
+
+// the indices of an indexed edit or read: how many name no Gaussian comes back before anything is written (after ensure_inverse)
+hipError_t count_bad_indices(splat_ctx* c, uint64_t k, const unsigned int* index, unsigned int* bad) {
+    HIP_RET(hipMemsetAsync(c->upd_bad, 0, sizeof(unsigned int), c->stream));
+    launch_index_check(c->stream, k, c->n, index, c->upd_bad);
+    HIP_RET(hipGetLastError());
+    HIP_RET(hipMemcpyAsync(bad, c->upd_bad, sizeof *bad, hipMemcpyDeviceToHost, c->stream));
+    return hipStreamSynchronize(c->stream);
 }
 
 // what splat_select_device refuses before it looks at the context or touches HIP; nullptr: nothing
@@ -358,16 +367,93 @@ int splat_update_gaussians_device(splat_ctx* c, uint64_t k, const void* d_index,
     HIP_TRY(c, follow_producer(c, producer_stream));
     // the indices first: the count of those that name no Gaussian comes back before anything is written
     unsigned int bad = 0;
-    HIP_TRY(c, hipMemsetAsync(c->upd_bad, 0, sizeof(unsigned int), c->stream));
-    launch_index_check(c->stream, k, n, index, c->upd_bad);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(&bad, c->upd_bad, sizeof bad, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, count_bad_indices(c, k, index, &bad));
     if (bad) return fail(c, SPLAT_ERR_INVALID, "an index is not below n; nothing was applied");
     const bool rebound = (fields & (SPLAT_FIELD_POS | SPLAT_FIELD_COV3D)) != 0;
     launch_repack_indexed(c->stream, n, k, index, fields, (const float*)d_pos4, (const float*)d_cov3d, (const float*)d_opacity,
                           (const float*)d_sh, c->inv, c->planes, rebound ? c->upd_dirty : nullptr);
     if (rebound) launch_plane_bounds(c->stream, n, c->planes, c->upd_dirty, c->bounds);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    scene_edited(c);
+    return SPLAT_OK;
+}
+
+// The inverses of the two edits: the named fields of the resident scene into the caller's device buffers.  They READ the
+// scene as a selection does -- behind the frames in flight, nothing of a frame's state touched -- and refuse what the edits
+// refuse (update_refusal).
+int splat_read_scene_device(splat_ctx* c, uint64_t n, uint32_t fields, void* d_pos4, void* d_cov3d, void* d_opacity, void* d_sh) {
+    if (!c) return fail(c, SPLAT_ERR_INVALID, "NULL context");
+    if (const char* why = update_refusal(n, fields, d_pos4, d_cov3d, d_opacity, d_sh)) return fail(c, SPLAT_ERR_INVALID, why);
+    if (c->n == 0) return fail(c, SPLAT_ERR_NO_SCENE, "no resident scene to read");
+    if (n != c->n) return fail(c, SPLAT_ERR_INVALID, "n is not the resident scene's");
+    if (fields == 0) return SPLAT_OK;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    int rc = ctx_quiesce(c);
+    if (rc != SPLAT_OK) return rc;
+    launch_unpack_scene(c->stream, n, fields, (float*)d_pos4, (float*)d_cov3d, (float*)d_opacity, (float*)d_sh, c->orig, c->planes);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SPLAT_OK;
+}
+
+int splat_read_gaussians_device(splat_ctx* c, uint64_t k, const void* d_index, uint32_t fields, void* d_pos4, void* d_cov3d,
+                                void* d_opacity, void* d_sh, void* producer_stream) {
+    if (!c) return fail(c, SPLAT_ERR_INVALID, "NULL context");
+    if (const char* why = update_refusal(k, fields, d_pos4, d_cov3d, d_opacity, d_sh)) return fail(c, SPLAT_ERR_INVALID, why);
+    if (k && !d_index) return fail(c, SPLAT_ERR_INVALID, "NULL index");
+    if (c->n == 0) return fail(c, SPLAT_ERR_NO_SCENE, "no resident scene to read");
+    if (k > c->n) return fail(c, SPLAT_ERR_INVALID, "more indices than Gaussians: the rows could not go back as an update");
+    if (fields == 0 || k == 0) return SPLAT_OK;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    int rc = ctx_quiesce(c);
+    if (rc != SPLAT_OK) return rc;
+    const unsigned int* index = (const unsigned int*)d_index;
+    HIP_TRY(c, ensure_inverse(c));
+    HIP_TRY(c, follow_producer(c, producer_stream));
+    unsigned int bad = 0;
+    HIP_TRY(c, count_bad_indices(c, k, index, &bad));
+    if (bad) return fail(c, SPLAT_ERR_INVALID, "an index is not below n; nothing was written");
+    launch_unpack_indexed(c->stream, c->n, k, index, fields, (float*)d_pos4, (float*)d_cov3d, (float*)d_opacity, (float*)d_sh, c->inv,
+                          c->planes);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SPLAT_OK;
+}
+
+// An affine map applied where the values lie: an edit like the two above it, with nothing taken from the caller but the
+// twelve floats.  Positions and covariances change, so the bounds are always made again.
+int splat_transform_scene_device(splat_ctx* c, const float m[12]) {
+    if (!c) return fail(c, SPLAT_ERR_INVALID, "NULL context");
+    if (!m) return fail(c, SPLAT_ERR_INVALID, "NULL matrix");
+    if (c->n == 0) return fail(c, SPLAT_ERR_NO_SCENE, "no resident scene to transform");
+    int rc = end_frames_for_edit(c);
+    if (rc != SPLAT_OK) return rc;
+    launch_transform_scene(c->stream, c->n, m, c->planes);
+    launch_plane_bounds(c->stream, c->n, c->planes, nullptr, c->bounds);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    scene_edited(c);
+    return SPLAT_OK;
+}
+
+int splat_transform_gaussians_device(splat_ctx* c, uint64_t k, const void* d_index, const float m[12], void* producer_stream) {
+    if (!c) return fail(c, SPLAT_ERR_INVALID, "NULL context");
+    if (!m) return fail(c, SPLAT_ERR_INVALID, "NULL matrix");
+    if (k && !d_index) return fail(c, SPLAT_ERR_INVALID, "NULL index");
+    if (c->n == 0) return fail(c, SPLAT_ERR_NO_SCENE, "no resident scene to transform");
+    if (k > c->n) return fail(c, SPLAT_ERR_INVALID, "more indices than Gaussians: they cannot be distinct");
+    if (k == 0) return SPLAT_OK;
+    int rc = end_frames_for_edit(c);
+    if (rc != SPLAT_OK) return rc;
+    const unsigned int* index = (const unsigned int*)d_index;
+    HIP_TRY(c, ensure_inverse(c));
+    HIP_TRY(c, follow_producer(c, producer_stream));
+    unsigned int bad = 0;
+    HIP_TRY(c, count_bad_indices(c, k, index, &bad));
+    if (bad) return fail(c, SPLAT_ERR_INVALID, "an index is not below n; nothing was applied");
+    launch_transform_indexed(c->stream, c->n, k, index, m, c->inv, c->planes, c->upd_dirty);
+    launch_plane_bounds(c->stream, c->n, c->planes, c->upd_dirty, c->bounds);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     scene_edited(c);

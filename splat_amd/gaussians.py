@@ -98,6 +98,17 @@ class DeviceGaussians:
         self._r.update_device(n=self.n, **{f: getattr(self, f) for f in (fields or shown)})
         return self
 
+    def pull(self, *fields):
+        """the inverse of refresh(): these buffers overwritten with the renderer's resident values (Renderer.read_device) --
+        the named ones among "positions", "cov3d", "opacities", "sh", all four when none is named.  The renderer's scene must
+        have this object's n.  What a transform or an indexed edit did to the scene shows here afterwards."""
+        shown = ("positions", "cov3d", "opacities", "sh")
+        for f in fields:
+            if f not in shown:
+                raise ValueError("pull: %r is not one of %s" % (f, ", ".join(shown)))
+        self._r.read_device(n=self.n, **{f: getattr(self, f) for f in (fields or shown)})
+        return self
+
     def free(self):
         for k in self.FIELDS:
             if getattr(self, k, 0) and getattr(self._r, "_h", None):

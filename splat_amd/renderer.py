@@ -189,6 +189,23 @@ class Renderer:
         """splat_update_gaussians_device: the same for the k Gaussians index[0..k) (uint32 / int32 original indices in device
         memory, distinct; k= with a plain address).  The field buffers are compact: row t belongs to Gaussian index[t].  An
         index >= n raises SplatError(ERR_INVALID) with nothing applied."""
+        k, pi = self._index_address(index, k)
+        mask, ptrs = self._update_fields(k, positions, cov3d, opacities, sh)
+        st = _producer_stream(stream, (index, positions, cov3d, opacities, sh))
+        self._check(self._L.splat_update_gaussians_device(self._h, k, C.c_void_p(pi), mask, *[C.c_void_p(p) for p in ptrs],
+                                                          C.c_void_p(st)))
+
+    def read_device(self, positions=None, cov3d=None, opacities=None, sh=None, n=None):
+        """splat_read_scene_device, the inverse of update_device: the resident values of the fields that are not None into the
+        caller's writable device buffers (layouts and addresses as in upload_device), rows in original index order, bit for
+        bit what the uploads and edits put there; positions get w = 1.  The others are not touched.  Synchronous; reads the
+        scene only: the frames in flight come first and nothing kept from frame to frame is lost."""
+        n = self.n if n is None else int(n)
+        mask, ptrs = self._update_fields(n, positions, cov3d, opacities, sh)
+        self._check(self._L.splat_read_scene_device(self._h, n, mask, *[C.c_void_p(p) for p in ptrs]))
+
+    def _index_address(self, index, k):
+        """(k, address) of k 32-bit indices in device memory: k from numel() unless given"""
         if k is None:
             if isinstance(index, int) or not hasattr(index, "numel"):
                 raise TypeError("k= is required with a plain device address")
@@ -196,11 +213,39 @@ class Renderer:
         k = int(k)
         if not isinstance(index, int) and hasattr(index, "element_size") and int(index.element_size()) != 4:
             raise TypeError("index: 32-bit indices expected, got %s" % getattr(index, "dtype", None))
-        pi = _device_address(index, "index", k, int(self.config.device), any_dtype=True)
+        return k, _device_address(index, "index", k, int(self.config.device), any_dtype=True)
+
+    def read_indexed(self, index, positions=None, cov3d=None, opacities=None, sh=None, stream=None, k=None):
+        """splat_read_gaussians_device, the inverse of update_indexed: compact rows, row t = Gaussian index[t] (uint32 / int32
+        original indices in device memory, in any order, duplicates allowed; k= with a plain address).  stream: where the
+        indices were written.  An index >= n raises SplatError(ERR_INVALID) with nothing written."""
+        k, pi = self._index_address(index, k)
         mask, ptrs = self._update_fields(k, positions, cov3d, opacities, sh)
-        st = _producer_stream(stream, (index, positions, cov3d, opacities, sh))
-        self._check(self._L.splat_update_gaussians_device(self._h, k, C.c_void_p(pi), mask, *[C.c_void_p(p) for p in ptrs],
-                                                          C.c_void_p(st)))
+        st = _producer_stream(stream, (index,))
+        self._check(self._L.splat_read_gaussians_device(self._h, k, C.c_void_p(pi), mask, *[C.c_void_p(p) for p in ptrs],
+                                                        C.c_void_p(st)))
+
+    def transform(self, matrix, index=None, stream=None, k=None):
+        """splat_transform_scene_device / splat_transform_gaussians_device: the affine map `matrix` (world -> world; anything
+        that reshapes to 3x4 or to 4x4 with the last row 0 0 0 1, cast to float32) applied in place to the positions and
+        3D covariances (A S A^T) of the whole scene, or of the Gaussians index[0..k) (as in update_indexed: distinct).
+        Opacities and sh stay; sh is not rotated.  An edit like update_device: synchronous, frames in flight end first, and
+        the frames that follow are those of upload() of the mapped arrays, byte for byte."""
+        m = np.asarray(matrix, dtype=f32)
+        if m.size == 16:
+            m = m.reshape(4, 4)
+            if not np.array_equal(m[3], np.array([0, 0, 0, 1], f32)):
+                raise ValueError("matrix: the last row of a 4x4 must be 0 0 0 1 (an affine map)")
+            m = m[:3]
+        elif m.size != 12:
+            raise ValueError("matrix: 12 (3x4) or 16 (4x4) numbers expected, got %d" % m.size)
+        m = np.ascontiguousarray(m.reshape(12), f32)
+        if index is None:
+            self._check(self._L.splat_transform_scene_device(self._h, _fp(m)))
+            return
+        k, pi = self._index_address(index, k)
+        st = _producer_stream(stream, (index,))
+        self._check(self._L.splat_transform_gaussians_device(self._h, k, C.c_void_p(pi), _fp(m), C.c_void_p(st)))
 
     # ---- selections ---------------------------------------------------------------------
     _SEL_OPS = {"set": _lib.SEL_OP_SET, "add": _lib.SEL_OP_ADD, "subtract": _lib.SEL_OP_SUBTRACT, "intersect": _lib.SEL_OP_INTERSECT}
