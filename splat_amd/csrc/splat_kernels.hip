@@ -3668,7 +3668,9 @@ void launch_sort(const SortArgs& a) {
     const unsigned int grid_big = std::min(a.grids.big, n_tiles), grid_mid = std::min(a.grids.mid, n_tiles);
     if (grid_big) {
         // four workgroups per list: lists of 16385..65536 keys are sorted as runs of 16384 and merged
-        // (two-pass binning only: one-pass buckets hold at most 16384 keys and there is no keys2)
+        // through the second key buffer, which both binning paths have (prepare_binning): two-pass binning's mirrors the
+        // first, list for list; one-pass binning's holds a region for every list of more than 2048 keys, found through off2
+        // -- a region of the first buffer may hold a list of any length
         const unsigned int grid_long = keys2 ? std::min(a.grids.lng, grid_big) : 0u;
         hipLaunchKernelGGL((sort_tiles_kernel<1024, 16384>), dim3(grid_big + 3u * grid_long), dim3(1024), (sort_lds_bytes<1024, 16384>()), s,
                            offsets, order, lens, keys, keys2, status, 8192u, radix_min, keys2 ? 4 : 1, grid_big, std::max(grid_long, 1u), orig, off2);
