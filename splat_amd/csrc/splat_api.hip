@@ -233,6 +233,7 @@ int ensure_bins(splat_ctx* c, unsigned int m) {
     HIP_TRY(c, dmalloc(c, &c->zero_layout, sizeof(unsigned int) * (size_t)(m + 1)));
     HIP_TRY(c, fill_now(c->zero_layout, 0, sizeof(unsigned int) * (size_t)(m + 1)));
     dfree(c->need_hint);
+    dfree(c->stage_nv); dfree(c->stage_mask);      // (made again, for the new tile count, by the next writer: composite_frame)
     HIP_TRY(c, dmalloc(c, &c->need_hint, hint_table(c, (size_t)(m + 1)).bytes()));
     HIP_TRY(c, fill_now(c->need_hint, 0, hint_table(c, (size_t)(m + 1)).bytes()));
     for (Slot& s : c->slots) {
@@ -662,6 +663,25 @@ int composite_frame(splat_ctx* c, const FrameLaunch& f, uint32_t* d_argb, bool w
         comp.lists.near_m = near ? s.near_m : nullptr; comp.keys.keys2 = near ? s.keys2 : nullptr;
     }
     comp.hints = hint_table(c);
+    // STAGING VERDICTS, kept from one retained frame to the next (CompArgs::stage_nv): the writer clears the counts -- once per
+    // rest, and whatever ends a retained set leads to a new writer -- and the frames composited from its lists, which run
+    // behind it on this stream, take and leave them.  Every other frame passes none.
+    if (c->knobs.dbg_stage_cache != 0u && f.retain == SPLAT_RETAIN_WRITER) {
+        const size_t waves = (size_t)c->m_alloc * 4u;
+        if (!c->stage_nv || !c->stage_mask) {
+            dfree(c->stage_nv); dfree(c->stage_mask);
+            HIP_TRY(c, dmalloc(c, &c->stage_nv, sizeof(unsigned int) * waves));
+            HIP_TRY(c, dmalloc(c, &c->stage_mask, sizeof(unsigned long long) * 32u * waves));
+        }
+        HIP_TRY(c, hipMemsetAsync(c->stage_nv, 0, sizeof(unsigned int) * waves, cs));
+        c->ret_set.frames = 0;
+    }
+    if (retained && c->knobs.dbg_stage_cache != 0u && c->stage_nv && c->stage_mask) {
+        comp.stage_nv = c->stage_nv; comp.stage_mask = c->stage_mask;
+        if (c->knobs.dbg_stage_cache == 2u && c->ret_set.frames >= 2u)
+            HIP_TRY(c, hipMemsetAsync(c->stage_mask, 0, sizeof(unsigned long long) * 32u * (size_t)c->m_alloc * 4u, cs));
+        c->ret_set.frames++;
+    }
     comp.refine = c->fc.close_width == 0.0f ? pd.refine : 0u;      // (exact modes only: a fast-mode frame depends on where its walks start)
     launch_composite(comp);
     c->last_near = retained ? c->ret_set.near_cap != 0u : pd.near_cap != 0u;
@@ -1223,6 +1243,7 @@ int splat_create(const splat_config* cfg, splat_ctx** out) {
     if (const char* k11 = std::getenv("SPLAT_DBG_KEYS2_ENTRIES")) c->knobs.dbg_keys2_entries = std::strtoull(k11, nullptr, 10);
     if (const char* k9 = std::getenv("SPLAT_DBG_HINT_RADIUS")) c->knobs.dbg_hint_radius = std::atoi(k9);
     if (const char* k12 = std::getenv("SPLAT_DBG_SELECT_BLIND")) c->knobs.dbg_select_blind = std::atoi(k12) != 0 ? 1u : 0u;
+    if (const char* k13 = std::getenv("SPLAT_DBG_STAGE_CACHE")) c->knobs.dbg_stage_cache = (unsigned int)std::min(2, std::max(0, std::atoi(k13)));
     if (const char* k5 = std::getenv("SPLAT_DBG_STARTS")) c->knobs.dbg_starts = std::atoi(k5) != 0 ? 1u : 0u;
     if (const char* k4 = std::getenv("SPLAT_COMP_LDS_PAD")) c->knobs.comp_lds_pad = (unsigned int)std::max(0, std::atoi(k4));
     if (const char* k1p = std::getenv("SPLAT_K1_LDS_PAD")) c->knobs.k1_lds_pad = (unsigned int)std::min(48 * 1024, std::max(0, std::atoi(k1p)));
@@ -1274,7 +1295,7 @@ void splat_destroy(splat_ctx* c) {
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);      // lane 1: compositors and gathers that use the buffers / the communicator released below
     if (c->comm) { comm_release(c->comm); c->comm = nullptr; }
     free_scene(c);
-    dfree(c->zero_layout); dfree(c->need_hint);
+    dfree(c->zero_layout); dfree(c->need_hint); dfree(c->stage_nv); dfree(c->stage_mask);
     for (Slot& s : c->slots) {
         dfree(s.counts); dfree(s.offsets); dfree(s.cursor); dfree(s.order); dfree(s.lens); dfree(s.counts_b); dfree(s.lay_a); dfree(s.lay_b);
         dfree(s.near_m); dfree(s.redo_layout); dfree(s.redo_cursors); dfree(s.off2);

@@ -166,7 +166,12 @@ struct splat_ctx {
         int slot = -1, ring = -1;
         unsigned int near_cap = 0;
         splat::FrameStatus status{};
+        unsigned int frames = 0;           // frames composited from the set so far (SPLAT_DBG_STAGE_CACHE=2 counts them)
     } ret_set;
+    // The staging verdicts the set's frames keep for each other (CompArgs::stage_nv / stage_mask): per tile 4 counts and
+    // 4 x 32 masks, m_alloc tiles, made when the first writer is launched, the counts cleared in front of every writer
+    unsigned int* stage_nv = nullptr;
+    unsigned long long* stage_mask = nullptr;
     int last_slot = -1;                    // buffer slot of the most recent frame (debug getters)
     bool last_lists_in_memory = false;     // ... and whether its compositor wrote the lists it sorted back to the buckets
     splat::FrameStatus* h_status = nullptr;  // pinned, one per event-ring entry

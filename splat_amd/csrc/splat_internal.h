@@ -119,6 +119,9 @@ struct LaunchKnobs {
     unsigned int dbg_select_blind = 0;     // SPLAT_DBG_SELECT_BLIND: the near selection ignores what the walks needed last frame (every selection is
                                            // near_cap keys: with a small near_cap the long tiles repair themselves on every binned frame -- tests)
     unsigned int dbg_starts = 0;           // SPLAT_DBG_STARTS: statistics frames record (list length, nearest keys the walk needed) per wave
+    unsigned int dbg_stage_cache = 1;      // SPLAT_DBG_STAGE_CACHE: 0 retained frames keep no staging verdicts; 2 the host zeroes the kept masks (not
+                                           // their counts) in front of every retained frame of a set after the second -- a frame that reads them
+                                           // then stages nothing there and comes out wrong: how a test sees that the path is live
 };
 
 // The per-tile hint table, kept from frame to frame: ONE allocation of HINT_WORDS planes of `stride` words (the context's
@@ -333,6 +336,8 @@ struct CompositeArgs {
                                     // starts(): where each wave's exact walk started, in keys from the list's near end (fc.start_hints);
                                     // refinement(): each wave's start refinement at rest (composite_tile, phase A)
     unsigned int refine;            // != 0: this frame's waves refine their starts (splat_policy_decision::refine)
+    unsigned int* stage_nv;         // a frame composited from retained lists: the staging verdicts its walks take from the frames before it
+    unsigned long long* stage_mask; // and leave for the next -- 4 words / 4 x 32 masks per tile (CompArgs); nullptr: none kept
 };
 void launch_composite(const CompositeArgs& a);
 // a frame composited from retained lists: its device status starts from these values (no scan ran to initialise it)

@@ -2783,9 +2783,14 @@ struct CompArgs {
     unsigned int* need_hint; unsigned int* start_hint; const unsigned int* off2;
     unsigned int* probe_hint;            // 4 words per tile beside start_hint: each wave's start refinement (see phase A); nullptr: none
     unsigned int refine;                 // != 0: a camera at rest refines its starts this frame -- bits 16..31 the rest's tag, 0..15 the frame
+    // STAGING VERDICTS KEPT FROM FRAME TO FRAME (frames composited from retained lists only; nullptr: off).  Per (tile, wave):
+    // stage_nv = how many end-aligned 64-record batches, counted from the near end of the list, have their verdicts in
+    // stage_mask (32 words per wave, word k = batch k's ballot) -- what the scan leaves in wmask for the walk behind it, left
+    // by one frame's walks for the next frame's (composite_tile: "verdicts of the last frame")
+    unsigned int* stage_nv; unsigned long long* stage_mask;
 };
 typedef const __attribute__((address_space(4))) CompArgs* KernArgs;       // (constant address space: uniform scalar loads)
-template <bool PAIR, bool LIBM>
+template <bool PAIR, bool LIBM, bool KEEP>
 static __device__ void repair_tile(KernArgs ka, unsigned int smem_lds, unsigned int exptab_lds, unsigned int item, bool again);
 
 // One tile (slot `item` of the longest-first tile order) by one workgroup; `smem` = sort_lds_bytes<256, 2048>() bytes.
@@ -2796,7 +2801,9 @@ static __device__ void repair_tile(KernArgs ka, unsigned int smem_lds, unsigned 
 //   1  this workgroup, in full (sort_long_list)
 //   2  NEAR SELECTION: this workgroup selects and sorts the nearest <= near_cap keys only; a wave whose walk needs more
 //      makes its tile repair itself: the workgroup sorts the whole list (flavour 1's code) and the waves that asked walk again
-template <bool PAIR, bool LIBM, int LONGM>
+// KEEP: a frame composited from retained lists (composite_retained_kernel) -- its walks take the staging verdicts the frames
+//   before it kept and keep their own (CompArgs::stage_nv).  Every other frame runs the code without any of it.
+template <bool PAIR, bool LIBM, int LONGM, bool KEEP = false>
 __device__ __forceinline__ void composite_tile(unsigned char* smem, const unsigned long long* exptab, const unsigned int item, const FrameConst& fc,
                                                const unsigned int* __restrict__ offsets, const unsigned int* __restrict__ order,
                                                const unsigned int* __restrict__ lens, unsigned long long* __restrict__ keys,
@@ -3044,6 +3051,26 @@ __device__ __forceinline__ void composite_tile(unsigned char* smem, const unsign
 
     bool need_far = false;                       // near selection: this wave's walk needs keys in front of the selection
     unsigned int itA = 0, itB = 0;               // (wave, record) iterations per phase, for the stats
+    // VERDICTS OF THE LAST FRAME.  A frame composited from retained lists walks the same records against the same block as the
+    // frame before it, and it does not scan: without these its exact walk would compute every staging verdict again (60 of a
+    // staging's 76 instructions).  The wave's masks of the last frames come back into wmask, as if a scan had left them:
+    // nvc of them (0xffffffff: the frame keeps none).  What the walks compute beyond them is kept at the walk's end.
+    unsigned int nvc = 0xffffffffu;
+    if constexpr (KEEP) {
+        if (!second_walk) {
+            const KernArgs kc = late();
+            const unsigned int* const nv_l = kc->stage_nv;
+            // (all 32 words are asked for beside the count, not behind it: one trip to memory; what lies behind the count is
+            // whatever an earlier rest left, and is dropped)
+            const unsigned long long kept = kc->stage_mask[(size_t)(tile * 4u + wave) * 32u + (lane & 31u)];
+            nvc = min((unsigned int)__builtin_amdgcn_readfirstlane((int)nv_l[tile * 4u + wave]), 32u);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            if (lane < nvc) wmask[lane] = kept;
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
     // ---------------- alpha pass: the alpha byte ----------------
     // blend() stores the NEW fragment's alpha (src/pipelines.rs:162-167), rejected fragments store 0,
     // so the byte is decided by each pixel's nearest covering record -- including the records that
@@ -3158,6 +3185,9 @@ __device__ __forceinline__ void composite_tile(unsigned char* smem, const unsign
         ws = (unsigned int)__builtin_amdgcn_readfirstlane((int)need);
         if (ws == 0xffffffffu) ws = end;          // no pixel of this strip is on the target
     }
+    // (a frame that scans keeps its scan's verdicts: it takes none from the last frame and leaves none)
+    const bool keeping = KEEP && nvc != 0xffffffffu && !scanned;
+    if (keeping) nA = nvc;
 
     // ---------------- phase B: exact compositing from the start layer ----------------
     // The bracket is closed when hi - lo <= cw on every channel of every pixel.  cw = 0: lo == hi, the exact frame.
@@ -3224,7 +3254,11 @@ __device__ __forceinline__ void composite_tile(unsigned char* smem, const unsign
             const unsigned int bs = bsN, cnt = cntN;
             const bool reuse = kb < nA;
             const unsigned int abase = (end - lb >= ((kb + 1u) << 6)) ? end - ((kb + 1u) << 6) : lb;   // where the scan's batch began
-            const unsigned int k = stage(r, cnt, bs, true, false, PAIR, reuse ? (int)kb : -1, bs - abase);
+            // (verdicts kept for the next frame: a WHOLE batch only -- the mask of a walk's partial first batch counts from
+            // `start`, not from where the batch begins.  With a near selection the batch clipped at `lb`, which begins elsewhere
+            // once the tile has repaired itself, is never whole: such a walk starts behind `lb`, or not at all.)
+            const bool keep = KEEP && keeping && !reuse && kb < 32u && bs == abase;
+            const unsigned int k = stage(r, cnt, bs, true, false, PAIR, reuse ? (int)kb : -1, bs - abase, keep ? (int)kb : -1);
             bsN = bs + cnt; cntN = min(64u, end - bsN); kb -= cntN ? 1u : 0u;
             if (cntN) fetch(bsN, cntN, r);                  // prefetch the next (nearer) batch
             if constexpr (PAIR) {
@@ -3307,6 +3341,23 @@ __device__ __forceinline__ void composite_tile(unsigned char* smem, const unsign
         if (!failed) start_l[tile * 4u + wave] = end - ws;
         kl->probe_hint[tile * 4u + wave] = (kl->refine & 0xffff0000u) | step;
     }
+    // ... and the verdicts the walk computed, for the next frame composited from these lists: the walk that completed went
+    // through every batch from the one `start` lies in to the nearest, all of them whole but perhaps the first
+    if (KEEP && keeping && !need_far && max(start, lb) < end) {
+        const unsigned int s = max(start, lb), kf = (end - 1u - s) >> 6;
+        const unsigned int ab = (end - lb >= ((kf + 1u) << 6)) ? end - ((kf + 1u) << 6) : lb;
+        const unsigned int nv_new = min(kf + (s == ab ? 1u : 0u), 32u);
+        unsigned int* const nv_l = kl->stage_nv;
+        const unsigned int nv_old = (unsigned int)__builtin_amdgcn_readfirstlane((int)nv_l[tile * 4u + wave]);
+        if (nv_new > nv_old) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            if (lane >= nv_old && lane < nv_new) kl->stage_mask[(size_t)(tile * 4u + wave) * 32u + lane] = wmask[lane];
+            if (lane == 0u) nv_l[tile * 4u + wave] = nv_new;
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
     if (need_far) return true;
     if (inside)
         kl->argb[(size_t)py * kl->fc.W + px] = ((uint32_t)A << 24) | ((uint32_t)R << 16) | ((uint32_t)G << 8) | (uint32_t)B;
@@ -3327,7 +3378,7 @@ __device__ __forceinline__ void composite_tile(unsigned char* smem, const unsign
         const bool again = walk_list();
         if (has_far && __syncthreads_or(again ? 1 : 0) != 0) {                // (has_far is uniform in the workgroup: the tile's near_m)
             if (tid == 0u) atomicAdd(&late()->status->n_near_fallback, 1u);
-            repair_tile<PAIR, LIBM>(ka, (unsigned int)(size_t)(__attribute__((address_space(3))) unsigned char*)smem,
+            repair_tile<PAIR, LIBM, KEEP>(ka, (unsigned int)(size_t)(__attribute__((address_space(3))) unsigned char*)smem,
                                     (unsigned int)(size_t)(__attribute__((address_space(3))) const unsigned long long*)exptab, item, again);
         }
     }
@@ -3338,7 +3389,7 @@ __device__ __forceinline__ void composite_tile(unsigned char* smem, const unsign
 // Everything but the workgroup's own state comes from the kernarg segment again; LDS addresses travel as offsets.
 // (static: with every caller in sight the compiler hands the kernel's seven-waves-per-SIMD register budget down to this
 // function -- 72 VGPRs, the rest on the stack -- instead of raising the kernel's to the 150 it would like.)
-template <bool PAIR, bool LIBM>
+template <bool PAIR, bool LIBM, bool KEEP>
 static __device__ __attribute__((noinline)) void repair_tile(KernArgs ka, unsigned int smem_lds, unsigned int exptab_lds, unsigned int item, bool again) {
     // (function arguments arrive in vector registers: make the uniform ones uniform again)
     const unsigned long long kp = uniform_u64((unsigned long long)(size_t)ka);
@@ -3361,6 +3412,10 @@ static __device__ __attribute__((noinline)) void repair_tile(KernArgs ka, unsign
     if (threadIdx.x == 0u) {
         const unsigned int tile = k->order[it];
         const_cast<unsigned int*>(k->near_m)[tile] = k->lens[tile];
+        // ... and that frame walks the region, not the selection: the verdicts its four waves kept counted from the selection's
+        // beginning (every wave of the tile is behind its first walk, and the second one keeps nothing)
+        unsigned int* const nv_l = KEEP ? k->stage_nv : nullptr;
+        if (nv_l != nullptr) { nv_l[tile * 4u + 0u] = 0u; nv_l[tile * 4u + 1u] = 0u; nv_l[tile * 4u + 2u] = 0u; nv_l[tile * 4u + 3u] = 0u; }
     }
 }
 
@@ -3516,6 +3571,21 @@ __global__ __launch_bounds__(256, (LONGM != 0 && !PAIR) ? 7 : SPLAT_COMP_WAVES) 
     }
     composite_tile<PAIR, LIBM, LONGM>(smem, exptab, blockIdx.x, a.fc, a.offsets, a.order, a.lens, a.keys, a.recs, a.argb, a.status, a.fused_sort_max, a.radix_min, a.iters, a.keep_keys, a.orig,
                                       a.clear_first, a.keys2, a.near_m, a.need_hint, a.start_hint, a.off2, (KernArgs)__builtin_amdgcn_kernarg_segment_ptr());
+}
+// The same launch for a frame composited from retained lists whose walks keep their staging verdicts (composite_tile's KEEP;
+// a.stage_nv and a.stage_mask exist).  Such a frame reads its lists from memory as flavour 0 or 2 does; same budgets.
+template <bool PAIR, bool LIBM, int LONGM>
+__global__ __launch_bounds__(256, (LONGM != 0 && !PAIR) ? 7 : SPLAT_COMP_WAVES) __attribute__((amdgpu_num_sgpr(96))) void composite_retained_kernel(CompArgs a) {
+    static_assert(LONGM == 0 || LONGM == 2, "a retained frame's long lists are in order in their regions, or selections");
+    __shared__ __attribute__((aligned(16))) unsigned char smem[sort_lds_bytes<256, 2048>()];
+    __shared__ unsigned long long exptab[LIBM ? 32 : 1];
+    if (a.status->overflow) return;
+    if constexpr (LIBM) {
+        if (threadIdx.x < 32) exptab[threadIdx.x] = EXP2F_TAB[threadIdx.x];
+        __syncthreads();
+    }
+    composite_tile<PAIR, LIBM, LONGM, true>(smem, exptab, blockIdx.x, a.fc, a.offsets, a.order, a.lens, a.keys, a.recs, a.argb, a.status, a.fused_sort_max, a.radix_min, a.iters, a.keep_keys, a.orig,
+                                            a.clear_first, a.keys2, a.near_m, a.need_hint, a.start_hint, a.off2, (KernArgs)__builtin_amdgcn_kernarg_segment_ptr());
 }
 
 // ---------------------------------------------------------------------------
@@ -3717,8 +3787,19 @@ void launch_composite(const CompositeArgs& c) {
     a.fused_sort_max = c.fused_sort_max; a.radix_min = c.knobs->sort_radix_min; a.iters = c.iters; a.keep_keys = flags; a.clear_first = c.clear_first ? 1u : 0u;
     a.orig = c.orig; a.keys2 = keys2; a.near_m = near_m; a.need_hint = near ? need_hint : nullptr; a.start_hint = start_hint; a.off2 = off2;
     a.probe_hint = probe_hint; a.refine = (probe_hint != nullptr && start_hint != nullptr) ? c.refine : 0u;
+    // (verdicts are kept by the flavours a retained frame takes: 0 and 2)
+    const bool keep_verdicts = c.stage_nv != nullptr && c.stage_mask != nullptr && (near || keys2 == nullptr);
+    a.stage_nv = keep_verdicts ? c.stage_nv : nullptr; a.stage_mask = keep_verdicts ? c.stage_mask : nullptr;
     auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(n_tiles), dim3(256), pad, c.s, a); };
-    if (near) {         // (a tile the selection does not serve repairs itself: no launch behind this one)
+    if (keep_verdicts && near) {
+        if (c.libm_exp) go(composite_retained_kernel<false, true, 2>);
+        else if (c.pair_walk) go(composite_retained_kernel<true, false, 2>);
+        else go(composite_retained_kernel<false, false, 2>);
+    } else if (keep_verdicts) {
+        if (c.libm_exp) go(composite_retained_kernel<false, true, 0>);
+        else if (c.pair_walk) go(composite_retained_kernel<true, false, 0>);
+        else go(composite_retained_kernel<false, false, 0>);
+    } else if (near) {         // (a tile the selection does not serve repairs itself: no launch behind this one)
         if (c.libm_exp) go(composite_exact_kernel<false, true, 2>);
         else if (c.pair_walk) go(composite_exact_kernel<true, false, 2>);
         else go(composite_exact_kernel<false, false, 2>);
