@@ -670,14 +670,17 @@ int composite_frame(splat_ctx* c, const FrameLaunch& f, uint32_t* d_argb, bool w
         const size_t waves = (size_t)c->m_alloc * 4u;
         if (!c->stage_nv || !c->stage_mask) {
             dfree(c->stage_nv); dfree(c->stage_mask);
-            HIP_TRY(c, dmalloc(c, &c->stage_nv, sizeof(unsigned int) * waves));
+            HIP_TRY(c, dmalloc(c, &c->stage_nv, sizeof(unsigned int) * 2u * waves));       // (the counts, then the proven starts)
             HIP_TRY(c, dmalloc(c, &c->stage_mask, sizeof(unsigned long long) * 32u * waves));
         }
-        HIP_TRY(c, hipMemsetAsync(c->stage_nv, 0, sizeof(unsigned int) * waves, cs));
+        HIP_TRY(c, hipMemsetAsync(c->stage_nv, 0, sizeof(unsigned int) * 2u * waves, cs));
         c->ret_set.frames = 0;
     }
     if (retained && c->knobs.dbg_stage_cache != 0u && c->stage_nv && c->stage_mask) {
         comp.stage_nv = c->stage_nv; comp.stage_mask = c->stage_mask;
+        // PROVEN STARTS (CompArgs::proven_start), behind the counts in one allocation: cleared with them by the set's writer,
+        // written and read by the set's frames alone.  Exact modes only: a fast-mode frame depends on where its walks start.
+        if (c->knobs.dbg_proven_starts != 0u && c->fc.close_width == 0.0f) comp.proven_start = c->proven_start();
         if (c->knobs.dbg_stage_cache == 2u && c->ret_set.frames >= 2u)
             HIP_TRY(c, hipMemsetAsync(c->stage_mask, 0, sizeof(unsigned long long) * 32u * (size_t)c->m_alloc * 4u, cs));
         c->ret_set.frames++;
@@ -1243,6 +1246,8 @@ int splat_create(const splat_config* cfg, splat_ctx** out) {
     if (const char* k11 = std::getenv("SPLAT_DBG_KEYS2_ENTRIES")) c->knobs.dbg_keys2_entries = std::strtoull(k11, nullptr, 10);
     if (const char* k9 = std::getenv("SPLAT_DBG_HINT_RADIUS")) c->knobs.dbg_hint_radius = std::atoi(k9);
     if (const char* k12 = std::getenv("SPLAT_DBG_SELECT_BLIND")) c->knobs.dbg_select_blind = std::atoi(k12) != 0 ? 1u : 0u;
+    if (const char* k15 = std::getenv("SPLAT_DBG_PROVEN_STARTS")) c->knobs.dbg_proven_starts = (unsigned int)std::min(2, std::max(0, std::atoi(k15)));
+    if (const char* k14 = std::getenv("SPLAT_DBG_BRACKET_COUNT")) c->knobs.dbg_bracket_count = std::atoi(k14) != 0 ? 1u : 0u;
     if (const char* k13 = std::getenv("SPLAT_DBG_STAGE_CACHE")) c->knobs.dbg_stage_cache = (unsigned int)std::min(2, std::max(0, std::atoi(k13)));
     if (const char* k5 = std::getenv("SPLAT_DBG_STARTS")) c->knobs.dbg_starts = std::atoi(k5) != 0 ? 1u : 0u;
     if (const char* k4 = std::getenv("SPLAT_COMP_LDS_PAD")) c->knobs.comp_lds_pad = (unsigned int)std::max(0, std::atoi(k4));
@@ -1851,6 +1856,10 @@ int splat_get_records(splat_ctx* c, splat_record* out, uint64_t n) {
     for (uint64_t j = 0; j < n; ++j) {          // everything lives in slot order; the caller gets original order
         const uint64_t i = c->h_orig[j];
         splat_record& o = out[i];
+        // K1 stores a record only for a Gaussian that reaches the slab's rows (in_slab); the slot's word for any other is
+        // whatever an earlier frame or the allocation left there: such a record reads as zeros, in every slot alike
+        const bool on_target = q[j].x <= q[j].y && q[j].z <= q[j].w;
+        if (!(on_target && std::max((int)q[j].z, c->fc.row_px0) <= std::min((int)q[j].w, c->fc.row_px1 - 1))) r[j] = Rec{};
         o.cx = r[j].a.x; o.cy = r[j].a.y; o.hx = r[j].a.z; o.hy = r[j].a.w;
         o.conic_a = r[j].b.x; o.conic_b = c->fc.y_up ? r[j].b.y : -r[j].b.y; o.conic_c = r[j].b.z; o.opacity = r[j].b.w;
         o.r = r[j].c.x; o.g = r[j].c.y; o.b = r[j].c.z; o.depth = d[j];

@@ -170,8 +170,11 @@ struct splat_ctx {
     } ret_set;
     // The staging verdicts the set's frames keep for each other (CompArgs::stage_nv / stage_mask): per tile 4 counts and
     // 4 x 32 masks, m_alloc tiles, made when the first writer is launched, the counts cleared in front of every writer
+    // ... and, behind the counts in the same allocation (one clear per writer), the starts the set has proven: one word per
+    // (tile, wave) again (CompArgs::proven_start)
     unsigned int* stage_nv = nullptr;
     unsigned long long* stage_mask = nullptr;
+    unsigned int* proven_start() const { return stage_nv ? stage_nv + (size_t)m_alloc * 4u : nullptr; }
     int last_slot = -1;                    // buffer slot of the most recent frame (debug getters)
     bool last_lists_in_memory = false;     // ... and whether its compositor wrote the lists it sorted back to the buckets
     splat::FrameStatus* h_status = nullptr;  // pinned, one per event-ring entry

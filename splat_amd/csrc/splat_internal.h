@@ -14,6 +14,9 @@
 #ifndef SPLAT_EXP_STAGE2
 #define SPLAT_EXP_STAGE2 0     // compositor: the staging verdicts computed twice (what they cost)
 #endif
+#ifndef SPLAT_EXP_NO_BRACKET
+#define SPLAT_EXP_NO_BRACKET 0 // compositor, retained frames: hinted exact walks skip the bracket, single-state from 0 (what the bracket costs at rest; invalid frames)
+#endif
 #ifndef SPLAT_EXP_K1DUMMY
 #define SPLAT_EXP_K1DUMMY 0    // K1: this many dummy VALU instructions per (Gaussian, tile) hand-out step (what per-pair verdicts would cost)
 #endif
@@ -119,7 +122,13 @@ struct LaunchKnobs {
     unsigned int dbg_select_blind = 0;     // SPLAT_DBG_SELECT_BLIND: the near selection ignores what the walks needed last frame (every selection is
                                            // near_cap keys: with a small near_cap the long tiles repair themselves on every binned frame -- tests)
     unsigned int dbg_starts = 0;           // SPLAT_DBG_STARTS: statistics frames record (list length, nearest keys the walk needed) per wave
-    unsigned int dbg_stage_cache = 1;      // SPLAT_DBG_STAGE_CACHE: 0 retained frames keep no staging verdicts; 2 the host zeroes the kept masks (not
+    unsigned int dbg_bracket_count = 0;    // SPLAT_DBG_BRACKET_COUNT: a statistics frame composited from retained lists reports, as n_iter_scan, the
+                                           // (wave, record) steps its walks took with both states of the bracket (a frame of that flavour
+                                           // that scans -- start hints off, a margin's scan turn -- reports its scan's steps PLUS those)
+    unsigned int dbg_proven_starts = 1;    // SPLAT_DBG_PROVEN_STARTS: 0 retained frames bracket every early-out walk, as binned frames do; 2 a walk that
+                                           // takes a proof starts from state 255 instead of 0 (the frame must be the same bytes).  The table
+                                           // lives with the kept staging verdicts: SPLAT_DBG_STAGE_CACHE=0 turns both off
+    unsigned int dbg_stage_cache = 1;      // SPLAT_DBG_STAGE_CACHE: 0 retained frames keep no staging verdicts (and take no proven starts); 2 the host zeroes the kept masks (not
                                            // their counts) in front of every retained frame of a set after the second -- a frame that reads them
                                            // then stages nothing there and comes out wrong: how a test sees that the path is live
 };
@@ -336,6 +345,7 @@ struct CompositeArgs {
                                     // starts(): where each wave's exact walk started, in keys from the list's near end (fc.start_hints);
                                     // refinement(): each wave's start refinement at rest (composite_tile, phase A)
     unsigned int refine;            // != 0: this frame's waves refine their starts (splat_policy_decision::refine)
+    unsigned int* proven_start;     // ... and the starts its set has proven (CompArgs::proven_start); nullptr: none
     unsigned int* stage_nv;         // a frame composited from retained lists: the staging verdicts its walks take from the frames before it
     unsigned long long* stage_mask; // and leave for the next -- 4 words / 4 x 32 masks per tile (CompArgs); nullptr: none kept
 };

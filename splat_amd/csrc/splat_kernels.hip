@@ -2788,6 +2788,10 @@ struct CompArgs {
     // stage_mask (32 words per wave, word k = batch k's ballot) -- what the scan leaves in wmask for the walk behind it, left
     // by one frame's walks for the next frame's (composite_tile: "verdicts of the last frame")
     unsigned int* stage_nv; unsigned long long* stage_mask;
+    // PROVEN STARTS (the same frames; nullptr: off).  Per (tile, wave): a walk's length from the list's end, in start_hint's
+    // units, from which a bracketed walk over this retained set's lists has closed; 0: none.  A walk that starts exactly
+    // there goes single-state (composite_tile: "a start this set has proven")
+    unsigned int* proven_start;
 };
 typedef const __attribute__((address_space(4))) CompArgs* KernArgs;       // (constant address space: uniform scalar loads)
 template <bool PAIR, bool LIBM, bool KEEP>
@@ -3274,6 +3278,21 @@ __device__ __forceinline__ void composite_tile(unsigned char* smem, const unsign
         return end;
     };
     unsigned int start = ws;
+    // A START THIS SET HAS PROVEN (frames composited from retained lists, exact mode).  The lists are the bytes the frame
+    // before walked, and a hinted walk starts where that frame's bracket closed: a bracket [0, 255] over the same records
+    // from the same start closes again, at the same batch -- the second state would prove what is proven.  blend() is monotone
+    // in the state, so EVERY state at `start` ends in the closed one: the walk goes single-state from there, from 0 (from 255
+    // with keep_keys bit 3, SPLAT_DBG_PROVEN_STARTS=2: the same frame, the claim tested from the other end).  Same end-aligned
+    // batches: the counts, the kept verdicts and the hints are what they were.  Any difference between the proof and this
+    // walk's start -- a hint rewritten by anything, a margin, a probe's shallower start -- sends the walk through the bracket.
+    // probe bit 29: this walk takes a proof (until its first step); bit 30: a bracketed run from the final `start` closed.
+    if constexpr (KEEP) {
+        if (cw == 0.0f && hinted && probe == 0u && !second_walk && start > lb) {
+            const KernArgs kp = late();
+            const unsigned int* const pv_l = kp->proven_start;
+            if (pv_l != nullptr && (unsigned int)__builtin_amdgcn_readfirstlane((int)pv_l[tile * 4u + wave]) == end - start) probe = 0x20000000u;
+        }
+    }
     while (!need_far) {
         if (start <= lb) {                            // nothing skipped: exact from the real pixel ...
             if (has_far) { need_far = true; break; }  // ... unless unsorted keys lie in front of the selection: the whole list, then
@@ -3281,14 +3300,30 @@ __device__ __forceinline__ void composite_tile(unsigned char* smem, const unsign
             run(std::false_type{}, lb);
             break;
         }
+#if SPLAT_EXP_NO_BRACKET
+        // timing experiment (invalid frames): what the bracket costs a frame at rest -- the walks that would carry it go single-state
+        if (KEEP && cw == 0.0f && hinted && probe == 0u && !second_walk) { R = G = B = 0.0f; run(std::false_type{}, start); break; }
+#endif
         // skipped layers [beg, start): bracket them
         R = G = B = 0.0f; R2 = G2 = B2 = 255.0f;
-        const unsigned int pos = run(std::true_type{}, start);
+        unsigned int pos = start;
+        if (KEEP && probe == 0x20000000u) {
+            // proven: the bracket reads as closed at `start`, on either end's state
+            if (late()->keep_keys & 8u) R = G = B = 255.0f;
+            R2 = R; G2 = G; B2 = B;
+        } else {
+            // (keep_keys bit 2, SPLAT_DBG_BRACKET_COUNT: the steps walked with both states, in the scan's counter -- a hinted
+            // walk does not scan.  The flag is read where it is used: nothing of it lives across the walk.)
+            if constexpr (KEEP) { if (late()->keep_keys & 4u) itA -= itB; }
+            pos = run(std::true_type{}, start);
+            if constexpr (KEEP) { if (late()->keep_keys & 4u) itA += itB; }
+        }
         const bool open = __builtin_amdgcn_ballot_w64(inside & ((R2 - R > cw) | (G2 - G > cw) | (B2 - B > cw))) != 0ull;
         if (!open) {
             // closed: continue single-state from the middle of the bracket (lo itself when lo == hi, the exact mode)
             R = truncf((R + R2) * 0.5f); G = truncf((G + G2) * 0.5f); B = truncf((B + B2) * 0.5f);
             if (pos < end) run(std::false_type{}, pos);
+            if constexpr (KEEP) probe = (probe & 0x20000000u) ? 0u : (probe | 0x40000000u);      // (a proof taken is in the table already)
             break;
         }
         // lo != hi somewhere at the end of the list: not proven.  A probe retries from the known-good start (counted apart
@@ -3334,12 +3369,20 @@ __device__ __forceinline__ void composite_tile(unsigned char* smem, const unsign
     }
     // ... and a probe's outcome: closed from the shallower start -> that is the new known-good one, the step stays; open -> the
     // retry above wrote where it closed instead, the step halves
+    const unsigned int closed_here = KEEP ? probe & 0x40000000u : 0u;
+    if constexpr (KEEP) probe &= 0x8000ffffu;
     if (probe != 0u && lane == 0u) {
         const bool failed = (probe >> 31) != 0u;
         const unsigned int half = (probe & 0xffffu) >> 1;
         const unsigned int step = failed ? (half >= (unsigned int)SPLAT_REFINE_MIN_STEP ? half : 0u) : probe;
         if (!failed) start_l[tile * 4u + wave] = end - ws;
         kl->probe_hint[tile * 4u + wave] = (kl->refine & 0xffff0000u) | step;
+    }
+    // ... and the proof: a bracket from the final `start` closed over this set's lists (a first try, a retry from the known-good
+    // start, a deeper retry, a probe that closed) -- the walk of the next frame that starts there needs no bracket
+    if constexpr (KEEP) {
+        unsigned int* const pv_l = kl->proven_start;
+        if (closed_here != 0u && !need_far && pv_l != nullptr && lane == 0u) pv_l[tile * 4u + wave] = end - start;
     }
     // ... and the verdicts the walk computed, for the next frame composited from these lists: the walk that completed went
     // through every batch from the one `start` lies in to the nearest, all of them whole but perhaps the first
@@ -3416,6 +3459,9 @@ static __device__ __attribute__((noinline)) void repair_tile(KernArgs ka, unsign
         // beginning (every wave of the tile is behind its first walk, and the second one keeps nothing)
         unsigned int* const nv_l = KEEP ? k->stage_nv : nullptr;
         if (nv_l != nullptr) { nv_l[tile * 4u + 0u] = 0u; nv_l[tile * 4u + 1u] = 0u; nv_l[tile * 4u + 2u] = 0u; nv_l[tile * 4u + 3u] = 0u; }
+        // ... and the starts they proved were proved over the selection's storage
+        unsigned int* const pv_l = KEEP ? k->proven_start : nullptr;
+        if (pv_l != nullptr) { pv_l[tile * 4u + 0u] = 0u; pv_l[tile * 4u + 1u] = 0u; pv_l[tile * 4u + 2u] = 0u; pv_l[tile * 4u + 3u] = 0u; }
     }
 }
 
@@ -3781,7 +3827,8 @@ void launch_composite(const CompositeArgs& c) {
     const unsigned int* near_m = c.lists.near_m;
     unsigned int *need_hint = c.hints.needs(), *start_hint = c.hints.starts(), *probe_hint = c.hints.refinement();
     const bool near = near_m != nullptr && keys2 != nullptr && need_hint != nullptr;
-    const unsigned int flags = (c.keep_keys ? 1u : 0u) | (c.knobs->dbg_starts ? 2u : 0u);
+    const unsigned int flags = (c.keep_keys ? 1u : 0u) | (c.knobs->dbg_starts ? 2u : 0u) | (c.knobs->dbg_bracket_count ? 4u : 0u) |
+                               (c.knobs->dbg_proven_starts == 2u ? 8u : 0u);
     CompArgs a;
     a.fc = c.fc; a.offsets = c.lists.offsets; a.order = c.lists.order; a.lens = c.lists.lens; a.keys = c.keys.keys; a.recs = c.recs; a.argb = c.argb; a.status = c.status;
     a.fused_sort_max = c.fused_sort_max; a.radix_min = c.knobs->sort_radix_min; a.iters = c.iters; a.keep_keys = flags; a.clear_first = c.clear_first ? 1u : 0u;
@@ -3790,6 +3837,7 @@ void launch_composite(const CompositeArgs& c) {
     // (verdicts are kept by the flavours a retained frame takes: 0 and 2)
     const bool keep_verdicts = c.stage_nv != nullptr && c.stage_mask != nullptr && (near || keys2 == nullptr);
     a.stage_nv = keep_verdicts ? c.stage_nv : nullptr; a.stage_mask = keep_verdicts ? c.stage_mask : nullptr;
+    a.proven_start = (keep_verdicts && c.fc.close_width == 0.0f) ? c.proven_start : nullptr;
     auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(n_tiles), dim3(256), pad, c.s, a); };
     if (keep_verdicts && near) {
         if (c.libm_exp) go(composite_retained_kernel<false, true, 2>);
