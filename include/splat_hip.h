@@ -42,7 +42,8 @@ extern "C" {
  * that wants them finds them by symbol (dlsym / hasattr) and does without them where they are missing.  Likewise
  * splat_update_scene_device and splat_update_gaussians_device (and the SPLAT_FIELD_* bits they take), and
  * splat_select_device and splat_selection_indices_device (and the splat_select_query and SPLAT_SEL_* values they take), and
- * splat_read_scene_device, splat_read_gaussians_device, splat_transform_scene_device and splat_transform_gaussians_device. */
+ * splat_read_scene_device, splat_read_gaussians_device, splat_transform_scene_device and splat_transform_gaussians_device, and
+ * splat_sh_rotation_blocks, splat_rotate_sh_scene_device and splat_rotate_sh_gaussians_device. */
 
 /* modes: bit flags, 0 = the default */
 #define SPLAT_MODE_EXACT 0       /* back-to-front, 8-bit truncation per splat as blend() does it; the exponential of
@@ -314,6 +315,38 @@ int splat_read_gaussians_device(splat_ctx* ctx, uint64_t k, const void* d_index,
  * rank's (splat_multi_ctx). */
 int splat_transform_scene_device(splat_ctx* ctx, const float m[12]);
 int splat_transform_gaussians_device(splat_ctx* ctx, uint64_t k, const void* d_index, const float m[12],
+                                     void* producer_stream);
+
+/* View-dependent colour TURNED WITH THE SCENE: what the transforms leave undone.  r: 3x3 row-major in HOST memory,
+ * R(i,k) = r[3i+k], world -> world -- the layout of the linear part of the transform's m.  The colour of a Gaussian is
+ * eval_sh(sh, dir): per channel 16 coefficients sh[3k + ch] in four bands, k = 0 | 1..3 | 4..8 | 9..15.  For an orthogonal R
+ * the rotated coefficients c' satisfy eval_sh(c', R d) == eval_sh(c, d) for every unit d: band 0 keeps its bits, band l is
+ * multiplied by a (2l+1) x (2l+1) block D_l(R),
+ *   c'_m = (((D(m,0) c_0 + D(m,1) c_1) + D(m,2) c_2) + ...)
+ * summed left to right, every product and every sum rounded to f32 once, unfused; every input of a band is read before any
+ * of its outputs is written.  Nothing in sh is checked: with a non-finite coefficient 0 * inf is NaN, so one inf or NaN
+ * makes its whole band of that channel NaN, also under the identity.
+ * splat_sh_rotation_blocks gives the f32 blocks, row-major (d_l[(2l+1) m + k] = D_l(m,k)): host only, no context, no GPU.
+ * They are derived in double from eval_sh's own polynomials and constants (this basis has its own signs and order): the
+ * least-squares solution of B_l D_l = B_l^R over 32 fixed directions on a Fibonacci spiral (B_l: the band's functions at
+ * d_i, B_l^R: at R^T d_i), every entry snapped to the nearest multiple of 2^-40 and then rounded to f32.  The snap (at most
+ * 4.6e-13) makes the blocks of the identity, of axis-aligned quarter turns and of axis mirrors exact signed permutations:
+ * the identity returns the values (a -0 may become +0), four quarter turns return the bits of every non-zero coefficient.
+ * r must be orthogonal; the library checks it in double on the f32 entries: every entry finite and max |R R^T - I| <= 1e-4
+ * (rotations made in f32 sit near 1e-7, a 1 % scale at 2e-2).  Otherwise SPLAT_ERR_INVALID and nothing is applied or
+ * written.  Reflections (det = -1) are accepted.
+ * The two device calls are EDITS and behave exactly as splat_update_* with SPLAT_FIELD_SH alone does: synchronous, the
+ * frames in flight complete first and show the scene as it was, the state kept from frame to frame starts over; positions
+ * and covariances stay, so the order and the K1 block bounds stay; the frames that follow are those of a fresh
+ * splat_upload_scene of the rotated arrays, byte for byte.  The indexed form checks the indices on the device before
+ * anything is written (an index >= n: SPLAT_ERR_INVALID, nothing applied) and makes the inverse order like the other
+ * indexed calls.  Duplicate indices are the caller's error: such a Gaussian may be turned once or twice; nothing faults.
+ * SPLAT_ERR_INVALID, before any device work: a NULL context or r (or d1, d2, d3), an r that is refused, k > 0 with a NULL
+ * d_index, k > n; SPLAT_ERR_NO_SCENE: no resident scene.  k == 0: SPLAT_OK, nothing done.
+ * The multi-GPU layer (splat_multi_*) has no counterpart, as for the updates: rotate each rank's (splat_multi_ctx). */
+int splat_sh_rotation_blocks(const float r[9], float d1[9], float d2[25], float d3[49]);
+int splat_rotate_sh_scene_device(splat_ctx* ctx, const float r[9]);
+int splat_rotate_sh_gaussians_device(splat_ctx* ctx, uint64_t k, const void* d_index, const float r[9],
                                      void* producer_stream);
 
 /* Debug / stage parity: the stored scene order and K1 block bounds of the current scene.

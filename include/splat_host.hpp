@@ -101,6 +101,13 @@ void read_gaussians_device(splat_ctx* ctx, uint64_t k, const void* d_index, uint
                            void* d_opacity, void* d_sh, void* producer_stream = nullptr);
 void transform_scene_device(splat_ctx* ctx, const float m[12]);
 void transform_gaussians_device(splat_ctx* ctx, uint64_t k, const void* d_index, const float m[12], void* producer_stream = nullptr);
+// ... and view-dependent colour turned with it (splat_sh_rotation_blocks, splat_rotate_sh_scene_device,
+// splat_rotate_sh_gaussians_device): r = 3x3 row-major orthogonal map in host memory (a reflection is fine); bands 1-3 of sh are
+// multiplied by the blocks sh_rotation_blocks gives (host only, no context; row-major 3x3, 5x5, 7x7), everything else keeps its
+// bits.  Edits like an update of sh alone.  Throw what the C calls refuse (an r that is not orthogonal among it).
+void sh_rotation_blocks(const float r[9], float d1[9], float d2[25], float d3[49]);
+void rotate_sh_scene_device(splat_ctx* ctx, const float r[9]);
+void rotate_sh_gaussians_device(splat_ctx* ctx, uint64_t k, const void* d_index, const float r[9], void* producer_stream = nullptr);
 
 struct GaussianList {           // src/gaussians.rs:408-416, SoA
     std::vector<float> positions;   // 4 x N (x,y,z,1)

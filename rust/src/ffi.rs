@@ -162,6 +162,13 @@ extern "C" {
     pub fn splat_transform_scene_device(ctx: *mut SplatCtx, m: *const f32) -> c_int;
     pub fn splat_transform_gaussians_device(ctx: *mut SplatCtx, k: u64, d_index: *const c_void, m: *const f32,
                                             producer_stream: *mut c_void) -> c_int;
+    // view-dependent colour turned with the scene (added under ABI 7, found by symbol): r = 3x3 row-major ORTHOGONAL map in HOST
+    // memory (max |R R^T - I| <= 1e-4, else SPLAT_ERR_INVALID; a reflection is fine); bands 1-3 of sh are multiplied by the
+    // blocks the first call returns (host only, no context: d1 3x3, d2 5x5, d3 7x7, row-major) -- an edit like an update of sh
+    pub fn splat_sh_rotation_blocks(r: *const f32, d1: *mut f32, d2: *mut f32, d3: *mut f32) -> c_int;
+    pub fn splat_rotate_sh_scene_device(ctx: *mut SplatCtx, r: *const f32) -> c_int;
+    pub fn splat_rotate_sh_gaussians_device(ctx: *mut SplatCtx, k: u64, d_index: *const c_void, r: *const f32,
+                                            producer_stream: *mut c_void) -> c_int;
     // debug / stage parity: the stored order (n u32) and the K1 block bounds (ceil(n/256) x 8 f32); either may be null
     pub fn splat_get_scene_layout(ctx: *mut SplatCtx, orig_out: *mut u32, n: u64, bounds_out: *mut f32, n_blocks: u64) -> c_int;
     pub fn splat_set_slab(ctx: *mut SplatCtx, tile_row0: i32, tile_row1: i32) -> c_int;

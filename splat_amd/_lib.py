@@ -97,6 +97,9 @@ SYMBOLS = [
                                               C.c_void_p, C.c_void_p]),
     ("splat_transform_scene_device", C.c_int, [C.c_void_p, _fp]),
     ("splat_transform_gaussians_device", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, _fp, C.c_void_p]),
+    ("splat_sh_rotation_blocks", C.c_int, [_fp, _fp, _fp, _fp]),
+    ("splat_rotate_sh_scene_device", C.c_int, [C.c_void_p, _fp]),
+    ("splat_rotate_sh_gaussians_device", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, _fp, C.c_void_p]),
     ("splat_get_scene_layout", C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint64, _fp, C.c_uint64]),
     ("splat_set_slab", C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     ("splat_tile_row_loads", C.c_int, [C.c_void_p, C.POINTER(CameraC), C.POINTER(C.c_uint64), C.c_int32]),

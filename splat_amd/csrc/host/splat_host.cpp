@@ -374,6 +374,20 @@ void transform_gaussians_device(splat_ctx* ctx, uint64_t k, const void* d_index,
     check(splat_transform_gaussians_device(ctx, k, d_index, m, producer_stream), ctx, "splat_transform_gaussians_device");
 }
 
+void sh_rotation_blocks(const float r[9], float d1[9], float d2[25], float d3[49]) {
+    check(splat_sh_rotation_blocks(r, d1, d2, d3), nullptr, "splat_sh_rotation_blocks");
+}
+
+void rotate_sh_scene_device(splat_ctx* ctx, const float r[9]) {
+    if (!ctx) throw std::runtime_error("rotate_sh_scene_device: no context");
+    check(splat_rotate_sh_scene_device(ctx, r), ctx, "splat_rotate_sh_scene_device");
+}
+
+void rotate_sh_gaussians_device(splat_ctx* ctx, uint64_t k, const void* d_index, const float r[9], void* producer_stream) {
+    if (!ctx) throw std::runtime_error("rotate_sh_gaussians_device: no context");
+    check(splat_rotate_sh_gaussians_device(ctx, k, d_index, r, producer_stream), ctx, "splat_rotate_sh_gaussians_device");
+}
+
 // load_from_ply (src/gaussians.rs:375-405): the AoS `Vec<Gaussian>` the reference returns, from the same decode
 std::vector<Gaussian> load_from_ply(const std::string& filename) {
     GaussianList l = load_from_ply_soa(filename, 0);

@@ -30,6 +30,8 @@
 #define SPLAT_EXP_K1DROP 0     // K1: 1 = close-up rectangles dropped from binning, n >= 2 = every rectangle of more than n tiles (invalid frames)
 #endif
 
+struct SplatShBlocks;             // the three sh rotation blocks (splat_sh_math.h)
+
 namespace splat {
 
 constexpr int TILE = SPLAT_TILE;
@@ -199,6 +201,11 @@ void launch_unpack_indexed(hipStream_t s, uint64_t n, uint64_t k, const unsigned
 void launch_transform_scene(hipStream_t s, uint64_t n, const float m[12], float4* planes);
 void launch_transform_indexed(hipStream_t s, uint64_t n, uint64_t k, const unsigned int* index, const float m[12],
                               const unsigned int* inv, float4* planes, unsigned char* dirty);
+// ... and bands 1-3 of sh turned by the blocks b (splat_sh_math.h) in every slot, or in the slots inv[index[t]]; nothing else
+// of a slot changes, so no bounds do
+void launch_rotate_sh_scene(hipStream_t s, uint64_t n, const SplatShBlocks& b, float4* planes);
+void launch_rotate_sh_indexed(hipStream_t s, uint64_t n, uint64_t k, const unsigned int* index, const SplatShBlocks& b,
+                              const unsigned int* inv, float4* planes);
 
 // A selection made from the resident scene (splat_select.hip).  SelectView: the camera and conventions the vertex stage's
 // geometry half needs -- a frame's, without slab, binning or compositor state.  The query arrives checked, its rectangle

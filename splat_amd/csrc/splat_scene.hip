@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "splat_context.h"
+#include "splat_sh_math.h"
 
 using namespace splat;
 
@@ -454,6 +455,61 @@ int splat_transform_gaussians_device(splat_ctx* c, uint64_t k, const void* d_ind
     if (bad) return fail(c, SPLAT_ERR_INVALID, "an index is not below n; nothing was applied");
     launch_transform_indexed(c->stream, c->n, k, index, m, c->inv, c->planes, c->upd_dirty);
     launch_plane_bounds(c->stream, c->n, c->planes, c->upd_dirty, c->bounds);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    scene_edited(c);
+    return SPLAT_OK;
+}
+
+// View-dependent colour turned with the scene: the sh counterpart of the transforms.  The blocks are made on the host
+// (splat_sh_math.h) from an r that has passed the orthogonality check; the device calls are edits of sh alone, so the
+// bounds stay.
+int splat_sh_rotation_blocks(const float r[9], float d1[9], float d2[25], float d3[49]) {
+    if (!r || !d1 || !d2 || !d3) return fail(nullptr, SPLAT_ERR_INVALID, "NULL pointer");
+    if (const char* why = sh_rotation_refusal(r)) return fail(nullptr, SPLAT_ERR_INVALID, why);
+    SplatShBlocks b;
+    sh_rotation_blocks(r, b);
+    std::copy(b.d1, b.d1 + 9, d1);
+    std::copy(b.d2, b.d2 + 25, d2);
+    std::copy(b.d3, b.d3 + 49, d3);
+    return SPLAT_OK;
+}
+
+int splat_rotate_sh_scene_device(splat_ctx* c, const float r[9]) {
+    if (!c) return fail(c, SPLAT_ERR_INVALID, "NULL context");
+    if (!r) return fail(c, SPLAT_ERR_INVALID, "NULL matrix");
+    if (const char* why = sh_rotation_refusal(r)) return fail(c, SPLAT_ERR_INVALID, why);
+    if (c->n == 0) return fail(c, SPLAT_ERR_NO_SCENE, "no resident scene to rotate");
+    SplatShBlocks b;
+    sh_rotation_blocks(r, b);
+    int rc = end_frames_for_edit(c);
+    if (rc != SPLAT_OK) return rc;
+    launch_rotate_sh_scene(c->stream, c->n, b, c->planes);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    scene_edited(c);
+    return SPLAT_OK;
+}
+
+int splat_rotate_sh_gaussians_device(splat_ctx* c, uint64_t k, const void* d_index, const float r[9], void* producer_stream) {
+    if (!c) return fail(c, SPLAT_ERR_INVALID, "NULL context");
+    if (!r) return fail(c, SPLAT_ERR_INVALID, "NULL matrix");
+    if (const char* why = sh_rotation_refusal(r)) return fail(c, SPLAT_ERR_INVALID, why);
+    if (k && !d_index) return fail(c, SPLAT_ERR_INVALID, "NULL index");
+    if (c->n == 0) return fail(c, SPLAT_ERR_NO_SCENE, "no resident scene to rotate");
+    if (k > c->n) return fail(c, SPLAT_ERR_INVALID, "more indices than Gaussians: they cannot be distinct");
+    if (k == 0) return SPLAT_OK;
+    SplatShBlocks b;
+    sh_rotation_blocks(r, b);
+    int rc = end_frames_for_edit(c);
+    if (rc != SPLAT_OK) return rc;
+    const unsigned int* index = (const unsigned int*)d_index;
+    HIP_TRY(c, ensure_inverse(c));
+    HIP_TRY(c, follow_producer(c, producer_stream));
+    unsigned int bad = 0;
+    HIP_TRY(c, count_bad_indices(c, k, index, &bad));
+    if (bad) return fail(c, SPLAT_ERR_INVALID, "an index is not below n; nothing was applied");
+    launch_rotate_sh_indexed(c->stream, c->n, k, index, b, c->inv, c->planes);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     scene_edited(c);

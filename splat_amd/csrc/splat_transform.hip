@@ -1,15 +1,19 @@
 // splat_transform.hip -- the resident scene read back and mapped where it lies (splat_read_scene_device,
-// splat_read_gaussians_device, splat_transform_scene_device, splat_transform_gaussians_device; gfx950).
+// splat_read_gaussians_device, splat_transform_scene_device, splat_transform_gaussians_device, splat_rotate_sh_scene_device,
+// splat_rotate_sh_gaussians_device; gfx950).
 //
 //   unpack_kernel<INDEXED>      the named fields' float slots of the planes into the caller's buffers: repack_kernel of
 //                               splat_update.hip run backwards, with the same slot map
 //   transform_kernel<INDEXED>   an affine map applied to the centre and the 3D covariance of a Gaussian, in place on the
 //                               planes (splat_transform_math.h); opacity and sh keep their bits
+//   rotate_sh_kernel<INDEXED>   bands 1-3 of the sh coefficients of a Gaussian turned by an orthogonal map, in place on the
+//                               planes (splat_sh_math.h); everything else keeps its bits
 //
-// Both are memory bound and need no LDS.  The order of the scene (orig[]) stays, as under every edit; the inverse of the
+// All three are memory bound and need no LDS.  The order of the scene (orig[]) stays, as under every edit; the inverse of the
 // order, the index check and the bounds from the planes are splat_update.hip's.
 #include "splat_internal.h"
 #include "splat_transform_math.h"
+#include "splat_sh_math.h"
 
 namespace splat {
 
@@ -91,6 +95,35 @@ void transform_kernel(uint64_t n, uint64_t rows, SplatAffine a, const unsigned i
 }
 
 // ---------------------------------------------------------------------------
+// Rotate sh.  sh[3..48) of slot j lies in planes 4-14 (plane p: sh[4p - 13 .. 4p - 10]) and in plane 15's .x (sh[47]): twelve
+// float4 loads, the three band products of splat_sh_math.h (249 multiply-adds), twelve float4 stores -- 384 bytes a Gaussian.
+// Plane 3 (cov[8] and band 0) is not touched; plane 15's .yzw go back as they came.  Every index into the 45 values is a
+// constant after unrolling, so they live in registers; the 83 block floats are a by-value argument.  Positions and
+// covariances stay, so no block bounds change and nothing is marked dirty.
+// INDEXED = false: thread j maps slot j (rows == n).  INDEXED = true: thread t maps slot inv[index[t]] (rows == k).
+// ---------------------------------------------------------------------------
+template <bool INDEXED>
+__global__ __launch_bounds__(256)
+void rotate_sh_kernel(uint64_t n, uint64_t rows, SplatShBlocks b, const unsigned int* __restrict__ index,
+                      const unsigned int* __restrict__ inv, float4* __restrict__ planes) {
+    const uint64_t t = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (t >= rows) return;
+    const uint64_t j = INDEXED ? (uint64_t)inv[index[t]] : t;
+    float4 v[12];
+#pragma unroll
+    for (int p = 0; p < 12; ++p) v[p] = planes[(uint64_t)(p + 4) * n + j];
+    float c[45];
+#pragma unroll
+    for (int p = 0; p < 11; ++p) { c[4 * p] = v[p].x; c[4 * p + 1] = v[p].y; c[4 * p + 2] = v[p].z; c[4 * p + 3] = v[p].w; }
+    c[44] = v[11].x;
+    rotate_sh_bands(b, c);
+#pragma unroll
+    for (int p = 0; p < 11; ++p) planes[(uint64_t)(p + 4) * n + j] = make_float4(c[4 * p], c[4 * p + 1], c[4 * p + 2], c[4 * p + 3]);
+    v[11].x = c[44];
+    planes[15 * n + j] = v[11];
+}
+
+// ---------------------------------------------------------------------------
 // launch wrappers
 // ---------------------------------------------------------------------------
 static inline unsigned int xf_blocks(uint64_t n) { return (unsigned int)((n + 255) / 256); }
@@ -125,6 +158,18 @@ void launch_transform_indexed(hipStream_t s, uint64_t n, uint64_t k, const unsig
                               const unsigned int* inv, float4* planes, unsigned char* dirty) {
     if (!k) return;
     hipLaunchKernelGGL(transform_kernel<true>, dim3(xf_blocks(k)), dim3(256), 0, s, n, k, xf_affine(m), index, inv, planes, dirty);
+}
+
+void launch_rotate_sh_scene(hipStream_t s, uint64_t n, const SplatShBlocks& b, float4* planes) {
+    if (!n) return;
+    hipLaunchKernelGGL(rotate_sh_kernel<false>, dim3(xf_blocks(n)), dim3(256), 0, s, n, n, b, (const unsigned int*)nullptr,
+                       (const unsigned int*)nullptr, planes);
+}
+
+void launch_rotate_sh_indexed(hipStream_t s, uint64_t n, uint64_t k, const unsigned int* index, const SplatShBlocks& b,
+                              const unsigned int* inv, float4* planes) {
+    if (!k) return;
+    hipLaunchKernelGGL(rotate_sh_kernel<true>, dim3(xf_blocks(k)), dim3(256), 0, s, n, k, b, index, inv, planes);
 }
 
 }  // namespace splat

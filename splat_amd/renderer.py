@@ -88,6 +88,27 @@ def _producer_stream(stream, args):
     return 0
 
 
+def _rotation3(rotation):
+    r = np.asarray(rotation, dtype=f32)
+    if r.size != 9:
+        raise ValueError("rotation: 9 (3x3) numbers expected, got %d" % r.size)
+    return np.ascontiguousarray(r.reshape(9), f32)
+
+
+def sh_rotation_blocks(rotation):
+    """splat_sh_rotation_blocks: (D1 [3,3], D2 [5,5], D3 [7,7]) float32, the blocks that bands 1-3 of a channel's sh
+    coefficients (sh[3k + ch], k = 1..3 | 4..8 | 9..15) are multiplied by when the scene is turned by `rotation` (world ->
+    world, anything that reshapes to 3x3, cast to float32): c'_m = sum_k D(m,k) c_k, so that eval_sh(c', R d) == eval_sh(c, d).
+    Host only: needs neither a Renderer nor a GPU.  ValueError unless the matrix is orthogonal (every entry finite,
+    max |R R^T - I| <= 1e-4; a reflection is fine)."""
+    r = _rotation3(rotation)
+    d = [np.zeros((n, n), f32) for n in (3, 5, 7)]
+    L = _lib.lib()
+    if L.splat_sh_rotation_blocks(_fp(r), *[_fp(a) for a in d]) != _lib.SPLAT_OK:
+        raise ValueError("rotation: %s" % (L.splat_last_error(None) or b"").decode())
+    return tuple(d)
+
+
 class Renderer:
     """One context = one GPU = one stream.  `conventions` overrides splat_default_config fields
     (y_up, sample_half, zclip, zmin, zmax)."""
@@ -225,12 +246,14 @@ class Renderer:
         self._check(self._L.splat_read_gaussians_device(self._h, k, C.c_void_p(pi), mask, *[C.c_void_p(p) for p in ptrs],
                                                         C.c_void_p(st)))
 
-    def transform(self, matrix, index=None, stream=None, k=None):
+    def transform(self, matrix, index=None, stream=None, k=None, rotate_sh=False):
         """splat_transform_scene_device / splat_transform_gaussians_device: the affine map `matrix` (world -> world; anything
         that reshapes to 3x4 or to 4x4 with the last row 0 0 0 1, cast to float32) applied in place to the positions and
         3D covariances (A S A^T) of the whole scene, or of the Gaussians index[0..k) (as in update_indexed: distinct).
-        Opacities and sh stay; sh is not rotated.  An edit like update_device: synchronous, frames in flight end first, and
-        the frames that follow are those of upload() of the mapped arrays, byte for byte."""
+        Opacities and sh stay; sh is not rotated unless rotate_sh is true: then the linear part of `matrix` must be
+        orthogonal (judged as rotate_sh judges it, BEFORE anything is applied: ValueError, nothing changed) and the transform
+        is followed by rotate_sh of the same Gaussians with it.  An edit like update_device: synchronous, frames in flight end
+        first, and the frames that follow are those of upload() of the mapped arrays, byte for byte."""
         m = np.asarray(matrix, dtype=f32)
         if m.size == 16:
             m = m.reshape(4, 4)
@@ -240,12 +263,32 @@ class Renderer:
         elif m.size != 12:
             raise ValueError("matrix: 12 (3x4) or 16 (4x4) numbers expected, got %d" % m.size)
         m = np.ascontiguousarray(m.reshape(12), f32)
+        r = np.ascontiguousarray(m.reshape(3, 4)[:, :3])
+        if rotate_sh:
+            sh_rotation_blocks(r)                                  # ValueError unless orthogonal
         if index is None:
             self._check(self._L.splat_transform_scene_device(self._h, _fp(m)))
+        else:
+            k, pi = self._index_address(index, k)
+            st = _producer_stream(stream, (index,))
+            self._check(self._L.splat_transform_gaussians_device(self._h, k, C.c_void_p(pi), _fp(m), C.c_void_p(st)))
+        if rotate_sh:
+            self.rotate_sh(r, index, stream, k)
+
+    def rotate_sh(self, rotation, index=None, stream=None, k=None):
+        """splat_rotate_sh_scene_device / splat_rotate_sh_gaussians_device: view-dependent colour turned by the orthogonal
+        map `rotation` (world -> world; anything that reshapes to 3x3, cast to float32; a reflection is fine), in place, for
+        the whole scene or for the Gaussians index[0..k) (as in transform).  Bands 1-3 of sh are multiplied by the blocks of
+        sh_rotation_blocks(rotation); band 0 and every other field keep their bits, so eval_sh(sh', R d) == eval_sh(sh, d).
+        A matrix that is not orthogonal (max |R R^T - I| > 1e-4, or a non-finite entry) raises SplatError(ERR_INVALID) with
+        nothing applied.  An edit like update_device of sh alone."""
+        r = _rotation3(rotation)
+        if index is None:
+            self._check(self._L.splat_rotate_sh_scene_device(self._h, _fp(r)))
             return
         k, pi = self._index_address(index, k)
         st = _producer_stream(stream, (index,))
-        self._check(self._L.splat_transform_gaussians_device(self._h, k, C.c_void_p(pi), _fp(m), C.c_void_p(st)))
+        self._check(self._L.splat_rotate_sh_gaussians_device(self._h, k, C.c_void_p(pi), _fp(r), C.c_void_p(st)))
 
     # ---- selections ---------------------------------------------------------------------
     _SEL_OPS = {"set": _lib.SEL_OP_SET, "add": _lib.SEL_OP_ADD, "subtract": _lib.SEL_OP_SUBTRACT, "intersect": _lib.SEL_OP_INTERSECT}

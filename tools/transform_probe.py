@@ -3,6 +3,7 @@
 splat_transform_gaussians_device (1 %, 50 %, 100 % of the Gaussians selected), splat_read_scene_device and
 splat_read_gaussians_device (positions and covariances of the same rows) -- and, beside them, the route a caller had before:
 splat_update_gaussians_device of PRECOMPUTED positions and covariances for the same rows (computing them is not in it).
+Also splat_rotate_sh_scene_device and splat_rotate_sh_gaussians_device with the transform's rotation, whole and for the same rows.
 All on one context, with the same data, alternated in one run.
 usage: transform_probe.py [--out profiles/scene_transform.json] [--reps 21] [workload]     (default: C3, 1.5 M Gaussians)
 Per operation: the wall time of the synchronous call, median over the repetitions; K1's device time per frame from the
@@ -62,7 +63,9 @@ def device_array(a):
 
 
 out_pos, out_cov = device_alloc(16 * n), device_alloc(36 * n)
+ROT = np.ascontiguousarray(M[:, :3])
 OPS = [("transform_scene", lambda: R.transform(M)),
+       ("rotate_sh_scene", lambda: R.rotate_sh(ROT)),
        ("read_scene_pos_cov", lambda: R.read_device(positions=out_pos, cov3d=out_cov, n=n))]
 for pct in (1, 50, 100):
     k = n * pct // 100
@@ -71,7 +74,8 @@ for pct in (1, 50, 100):
     rows = dict(positions=device_array(g.positions[idx]), cov3d=device_array(g.cov3d[idx]))
     OPS += [("transform_indexed_%dpct" % pct, lambda a=a: R.transform(M, **a)),
             ("read_indexed_pos_cov_%dpct" % pct, lambda a=a: R.read_indexed(positions=out_pos, cov3d=out_cov, **a)),
-            ("update_indexed_pos_cov_%dpct" % pct, lambda a=a, rows=rows: R.update_indexed(**a, **rows))]
+            ("update_indexed_pos_cov_%dpct" % pct, lambda a=a, rows=rows: R.update_indexed(**a, **rows)),
+            ("rotate_sh_indexed_%dpct" % pct, lambda a=a: R.rotate_sh(ROT, **a))]
 
 
 def timed(fn):
@@ -83,7 +87,7 @@ def timed(fn):
 d.upload()
 for _ in range(3):                                    # key buffers, per-tile arrays, the inverse order: made before the clock starts
     R.render_frame_device(cam_c, image, sync=True)
-OPS[2][1]()
+OPS[3][1]()
 call = {name: [] for name, _ in OPS}
 k1 = []
 for _ in range(reps):
