@@ -43,7 +43,8 @@ extern "C" {
  * splat_update_scene_device and splat_update_gaussians_device (and the SPLAT_FIELD_* bits they take), and
  * splat_select_device and splat_selection_indices_device (and the splat_select_query and SPLAT_SEL_* values they take), and
  * splat_read_scene_device, splat_read_gaussians_device, splat_transform_scene_device and splat_transform_gaussians_device, and
- * splat_sh_rotation_blocks, splat_rotate_sh_scene_device and splat_rotate_sh_gaussians_device. */
+ * splat_sh_rotation_blocks, splat_rotate_sh_scene_device and splat_rotate_sh_gaussians_device, and
+ * splat_select_neighbours_device. */
 
 /* modes: bit flags, 0 = the default */
 #define SPLAT_MODE_EXACT 0       /* back-to-front, 8-bit truncation per splat as blend() does it; the exponential of
@@ -267,6 +268,51 @@ int splat_select_device(splat_ctx* ctx, const splat_select_query* q, const splat
  * d_index_out with n > 0 and capacity > 0. */
 int splat_selection_indices_device(splat_ctx* ctx, uint64_t n, const void* d_selection, void* d_index_out,
                                    uint64_t capacity, uint64_t* count_out, void* producer_stream);
+/* A selection BY NEIGHBOURHOOD: what no test on one Gaussian alone can say.  For every Gaussian i the call counts the other
+ * Gaussians of a source set whose centres lie within `radius` of its own, and i passes when the count lies in
+ * [count_min, count_max].  Floaters -- fewer than k neighbours within r: count_min = 0, count_max = k - 1.  Growing a
+ * selection by r: d_source = d_selection, count_min = 1, count_max = 0xFFFFFFFF, op = SPLAT_SEL_OP_ADD.
+ *   Distance  r2 = radius * radius, rounded to f32 once on the host.  For Gaussians i and j with RESIDENT centres p and q:
+ *             dx = p.x - q.x, dy and dz alike; d2 = (dx dx + dy dy) + dz dz, each product and sum rounded to f32 once,
+ *             unfused, in this order.  j is WITHIN REACH of i when d2 <= r2; a NaN fails.  The relation is symmetric bit for
+ *             bit.  A Gaussian with a non-finite coordinate is within nobody's reach and nobody is within its own (d2 is inf
+ *             or NaN, and r2 is finite).
+ *   Count     c_i = the number of j != i (different Gaussians: coincident centres do count each other) that are in the
+ *             source set and within reach of i.  The source set: the Gaussians whose byte in d_source is nonzero -- n bytes
+ *             at any byte address, ORIGINAL index order, exactly like a selection; d_source == NULL: all Gaussians.  With
+ *             count_max < 0xFFFFFFFF, c_i saturates at count_max + 1 (the library stops counting there).
+ *   Pass, op  i passes when count_min <= c_i <= count_max.  `op` (SPLAT_SEL_OP_*) combines the result with d_selection
+ *             exactly as splat_select_device does: the library writes only 0 and 1, ADD and SUBTRACT leave the bytes of
+ *             Gaussians that do not pass as they are.  *count_out (nullable): the Gaussians selected after the op.
+ *   Aliasing  d_source may be the very buffer d_selection is -- a selection grown in place: every source byte is read before
+ *             any selection byte is written (the op is applied by a kernel of its own, behind the counts).
+ *   Counts    d_counts_out (nullable): n u32, 4-byte aligned, ORIGINAL index order, receives the saturated c_i.
+ *             d_selection may be NULL when d_counts_out is given: counts only, `op` is not used (an unknown one is still
+ *             refused), and *count_out is the number of Gaussians that pass.  At least one of the two must be given.
+ *   Work      A large radius on a large scene is O(n^2), so the work is bounded before any of it is done.  The library first
+ *             counts the ORDERED pairs (target block, source block) of K1 blocks (256 consecutive slots: see
+ *             splat_get_scene_layout), a block paired with itself included, whose resident bounds are within reach of each
+ *             other: per axis g_a = max(max(lo_s[a] - hi_t[a], lo_t[a] - hi_s[a]), 0), and the pair counts when
+ *             (g0 g0 + g1 g1) + g2 g2 <= r2, in f32, unfused, in this order.  A block with NaN bounds (no finite centre)
+ *             is in no pair; the source mask plays no part.  *block_pairs_out (nullable) always receives that number.  When
+ *             max_block_pairs != 0 and the number exceeds it: SPLAT_ERR_CAPACITY, nothing is written to d_selection or
+ *             d_counts_out, and splat_last_error names both numbers.  0 = no limit.  The definition is exact, so a caller
+ *             can restate it from splat_get_scene_layout's bounds; each pair costs up to 256 x 256 point tests.
+ * The bounds only ever SKIP work: the gap above, evaluated in d2's order, is never larger than the d2 of any two centres
+ * inside the boxes (f32 subtraction, multiplication and addition round monotonically), so the result is the all-pairs
+ * result bit for bit -- also after edits, which recompute the bounds and leave the slot order stale.
+ * It READS the scene as splat_select_device does: synchronous, ordered on the context's stream behind the frames in flight
+ * (producer_stream: the stream that wrote d_source or d_selection), and the state kept from frame to frame, retained
+ * lists included, survives.  splat_device_bytes() is as before; the temporaries (16 bytes, and 4 n bytes of counts when
+ * d_counts_out is NULL) live for the call.
+ * SPLAT_ERR_INVALID, judged before the context is looked at: radius NaN, negative or infinite, or radius * radius not finite
+ * in f32; count_min > count_max; an unknown op; d_selection and d_counts_out both NULL; a misaligned d_counts_out.  Then a
+ * NULL context: SPLAT_ERR_INVALID; no resident scene: SPLAT_ERR_NO_SCENE.
+ * The multi-GPU layer needs no counterpart, as for splat_select_device: every rank holds the whole scene, so one rank's
+ * context (splat_multi_ctx) selects for all. */
+int splat_select_neighbours_device(splat_ctx* ctx, float radius, const void* d_source, uint32_t count_min, uint32_t count_max,
+                                   uint32_t op, void* d_selection, void* d_counts_out, uint64_t max_block_pairs,
+                                   uint64_t* block_pairs_out, uint64_t* count_out, void* producer_stream);
 
 /* The resident values GIVEN BACK, and changed WHERE THEY LIE: with these two an editor that moves, rotates or scales a
  * selection keeps no copy of the scene (after an upload from PLY rows it never had one), and select -> indices -> transform,

@@ -108,6 +108,17 @@ void transform_gaussians_device(splat_ctx* ctx, uint64_t k, const void* d_index,
 void sh_rotation_blocks(const float r[9], float d1[9], float d2[25], float d3[49]);
 void rotate_sh_scene_device(splat_ctx* ctx, const float r[9]);
 void rotate_sh_gaussians_device(splat_ctx* ctx, uint64_t k, const void* d_index, const float r[9], void* producer_stream = nullptr);
+// A selection by neighbourhood on the resident scene (splat_select_neighbours_device): Gaussian i passes when the number of OTHER
+// Gaussians of the source set (d_source: n bytes, nonzero = source, null = all) with centres within `radius` of its own lies in
+// [count_min, count_max]; `op` = SPLAT_SEL_OP_* combines that with d_selection (one byte per Gaussian, original index order;
+// may be d_source itself).  d_counts_out (n u32, null = not wanted) receives the counts, saturated at count_max + 1;
+// d_selection may be null with it.  max_block_pairs bounds the work (0 = no limit; beyond it the C call's SPLAT_ERR_CAPACITY is
+// thrown and nothing is written); *block_pairs_out (nullable) receives the number it is compared with.  Returns how many are
+// selected after the op.  Floaters: select_neighbours(ctx, r, nullptr, 0, k - 1, SPLAT_SEL_OP_SET, sel, nullptr, limit);
+// grow: select_neighbours(ctx, r, sel, 1, 0xFFFFFFFFu, SPLAT_SEL_OP_ADD, sel, nullptr, limit).  Throws what the C call refuses.
+uint64_t select_neighbours(splat_ctx* ctx, float radius, const void* d_source, uint32_t count_min, uint32_t count_max, uint32_t op,
+                           void* d_selection, void* d_counts_out, uint64_t max_block_pairs, uint64_t* block_pairs_out = nullptr,
+                           void* producer_stream = nullptr);
 
 struct GaussianList {           // src/gaussians.rs:408-416, SoA
     std::vector<float> positions;   // 4 x N (x,y,z,1)

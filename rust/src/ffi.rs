@@ -150,6 +150,13 @@ extern "C" {
     // ... and its indices, ascending, as u32: a d_index for splat_update_gaussians_device; *count_out may exceed capacity
     pub fn splat_selection_indices_device(ctx: *mut SplatCtx, n: u64, d_selection: *const c_void, d_index_out: *mut c_void,
                                           capacity: u64, count_out: *mut u64, producer_stream: *mut c_void) -> c_int;
+    // ... and a selection by neighbourhood (added under ABI 7, found by symbol): Gaussian i passes when the other Gaussians of the
+    // source set (d_source: n bytes, null = all; may be d_selection itself) within `radius` of its centre number count_min ..=
+    // count_max; d_counts_out (n u32) and d_selection may be null, not both; max_block_pairs bounds the work (0 = no limit,
+    // beyond it SPLAT_ERR_CAPACITY with nothing written); block_pairs_out and count_out may be null
+    pub fn splat_select_neighbours_device(ctx: *mut SplatCtx, radius: f32, d_source: *const c_void, count_min: u32, count_max: u32,
+                                          op: u32, d_selection: *mut c_void, d_counts_out: *mut c_void, max_block_pairs: u64,
+                                          block_pairs_out: *mut u64, count_out: *mut u64, producer_stream: *mut c_void) -> c_int;
     // the resident values given back, and mapped where they lie (added under ABI 7, found by symbol like those above): the reads
     // are the updates' inverses (same layouts and SPLAT_FIELD_* bits; pos4 gets w = 1; a buffer whose field is not named may be
     // null and is left untouched) and read the scene as a selection does; m = 3x4 row-major affine map in HOST memory, applied

@@ -388,6 +388,17 @@ void rotate_sh_gaussians_device(splat_ctx* ctx, uint64_t k, const void* d_index,
     check(splat_rotate_sh_gaussians_device(ctx, k, d_index, r, producer_stream), ctx, "splat_rotate_sh_gaussians_device");
 }
 
+uint64_t select_neighbours(splat_ctx* ctx, float radius, const void* d_source, uint32_t count_min, uint32_t count_max, uint32_t op,
+                           void* d_selection, void* d_counts_out, uint64_t max_block_pairs, uint64_t* block_pairs_out,
+                           void* producer_stream) {
+    if (!ctx) throw std::runtime_error("select_neighbours: no context");
+    uint64_t count = 0;
+    check(splat_select_neighbours_device(ctx, radius, d_source, count_min, count_max, op, d_selection, d_counts_out, max_block_pairs,
+                                         block_pairs_out, &count, producer_stream),
+          ctx, "splat_select_neighbours_device");
+    return count;
+}
+
 // load_from_ply (src/gaussians.rs:375-405): the AoS `Vec<Gaussian>` the reference returns, from the same decode
 std::vector<Gaussian> load_from_ply(const std::string& filename) {
     GaussianList l = load_from_ply_soa(filename, 0);

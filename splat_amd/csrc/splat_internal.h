@@ -1,5 +1,5 @@
 // splat_internal.h -- shared between the host files (splat_api.hip, splat_scene.hip) and the kernel files (splat_kernels.hip,
-// splat_ply.hip, splat_update.hip, splat_select.hip).
+// splat_ply.hip, splat_update.hip, splat_select.hip, splat_neighbours.hip).
 #ifndef SPLAT_INTERNAL_H
 #define SPLAT_INTERNAL_H
 #include <hip/hip_runtime.h>
@@ -232,6 +232,16 @@ constexpr unsigned int SELECT_SCAN_ROUND = 256; // workgroup counts the scan tak
 inline uint64_t selection_groups(const void* mask, uint64_t n) { return (((uintptr_t)mask & 15u) + n + SELECT_SPAN - 1) / SELECT_SPAN; }
 void launch_selection_indices(hipStream_t s, uint64_t n, const unsigned char* mask, unsigned int* out, uint64_t capacity,
                               unsigned int* counts);
+// ... and a selection by neighbourhood (splat_neighbours.hip; r2: the radius squared, finite).  *pairs (zeroed by the caller) +=
+// the ordered pairs of K1 blocks whose bounds are within reach of each other.  counts[i] (n words, ORIGINAL index order) =
+// min(cap, the Gaussians j != i with source[j] != 0 -- source == nullptr: all -- whose centre is within reach of i's).
+// The apply step judges count_min <= counts[i] <= count_max and combines selection[i] as launch_select_query does;
+// selection == nullptr: nothing is written and the Gaussians that pass are counted.  *count (zeroed by the caller) += them.
+void launch_neighbour_block_pairs(hipStream_t s, uint64_t n, const BlockBounds* bounds, float r2, unsigned long long* pairs);
+void launch_neighbour_counts(hipStream_t s, uint64_t n, const float4* planes, const unsigned int* orig, const BlockBounds* bounds,
+                             const unsigned char* source, float r2, unsigned int cap, unsigned int* counts);
+void launch_neighbour_apply(hipStream_t s, uint64_t n, const unsigned int* counts, unsigned int count_min, unsigned int count_max,
+                            uint32_t op, unsigned char* selection, unsigned int* count);
 
 // ---- The per-frame launches take one argument block each, by const&.  The blocks are plain aggregates without defaults: a
 // caller value-initialises one (`ScanArgs a{};`) and what it does not set is zero / nullptr / false.  What travels together

@@ -1,14 +1,15 @@
 // splat_scene.hip -- everything that puts values into the resident scene: the uploads (host buffers, device buffers, PLY
 // rows), the in-place edits, K0 (cov3d) and the scene's layout read back -- and the selections read from it, which name the
 // Gaussians such an edit is for.  Host side only, no device code: the kernels are splat_kernels.hip's (order, bounds,
-// packing), splat_ply.hip's, splat_update.hip's, splat_transform.hip's and splat_select.hip's.  What the frame scheduler
-// (splat_api.hip) holds per scene is behind the seam of splat_context.h.
+// packing), splat_ply.hip's, splat_update.hip's, splat_transform.hip's, splat_select.hip's and splat_neighbours.hip's.
+// What the frame scheduler (splat_api.hip) holds per scene is behind the seam of splat_context.h.
 #include <algorithm>
 #include <cmath>
 #include <string>
 #include <vector>
 
 #include "splat_context.h"
+#include "splat_neighbour_math.h"
 #include "splat_sh_math.h"
 
 using namespace splat;
@@ -196,6 +197,18 @@ const char* select_refusal(const splat_select_query* q, const splat_camera* cam,
                                           cam->w != std::floor(cam->w) || cam->h != std::floor(cam->h)))
         return "camera w/h must be integers in [1, 65535]";
     if ((q->tests & SPLAT_SEL_SCREEN) && q->screen_rule == 1u && pixel_mask) return "a pixel mask goes with the centre rule, not with touch";
+    return nullptr;
+}
+
+// what splat_select_neighbours_device refuses before it looks at the context or touches HIP; nullptr: nothing
+const char* neighbours_refusal(float radius, uint32_t count_min, uint32_t count_max, uint32_t op, const void* selection,
+                               const void* counts_out) {
+    if (!(radius >= 0.0f)) return "radius is NaN or negative";
+    if (!std::isfinite(nb_radius2(radius))) return "radius: radius * radius is not finite in f32";
+    if (count_min > count_max) return "count_min is above count_max";
+    if (op > SPLAT_SEL_OP_INTERSECT) return "unknown op";
+    if (!selection && !counts_out) return "d_selection and d_counts_out are both NULL";
+    if ((uintptr_t)counts_out & 3u) return "d_counts_out is misaligned (4 bytes)";
     return nullptr;
 }
 
@@ -580,6 +593,47 @@ int splat_selection_indices_device(splat_ctx* c, uint64_t n, const void* d_selec
     HIP_TRY(c, hipMemcpyAsync(&count, d_counts + g, sizeof count, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     *count_out = count;
+    return SPLAT_OK;
+}
+
+// The selection by neighbourhood reads the scene as the one above does.  The work bound comes back first: nothing of the
+// caller's is written before the block pairs are known to be within max_block_pairs.
+int splat_select_neighbours_device(splat_ctx* c, float radius, const void* d_source, uint32_t count_min, uint32_t count_max, uint32_t op,
+                                   void* d_selection, void* d_counts_out, uint64_t max_block_pairs, uint64_t* block_pairs_out,
+                                   uint64_t* count_out, void* producer_stream) {
+    if (const char* why = neighbours_refusal(radius, count_min, count_max, op, d_selection, d_counts_out)) return fail(c, SPLAT_ERR_INVALID, why);
+    if (!c) return fail(c, SPLAT_ERR_INVALID, "NULL context");
+    if (c->n == 0) return fail(c, SPLAT_ERR_NO_SCENE, "no resident scene to select from");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    int rc = ctx_quiesce(c);
+    if (rc != SPLAT_OK) return rc;
+    const uint64_t n = c->n;
+    const float r2 = nb_radius2(radius);
+    const unsigned int cap = count_max < 0xFFFFFFFFu ? count_max + 1u : 0xFFFFFFFFu;
+    Temps t(c);
+    unsigned long long* d_pairs = nullptr;     // the block pairs, and behind them the count of what is selected
+    unsigned int* d_counts = (unsigned int*)d_counts_out;
+    unsigned long long pairs = 0;
+    unsigned int count = 0;
+    HIP_TRY(c, t.alloc(&d_pairs, 2 * sizeof(unsigned long long)));
+    unsigned int* const d_count = (unsigned int*)(d_pairs + 1);
+    HIP_TRY(c, hipMemsetAsync(d_pairs, 0, 2 * sizeof(unsigned long long), c->stream));
+    HIP_TRY(c, follow_producer(c, producer_stream));
+    launch_neighbour_block_pairs(c->stream, n, c->bounds, r2, d_pairs);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(&pairs, d_pairs, sizeof pairs, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (block_pairs_out) *block_pairs_out = pairs;
+    if (max_block_pairs != 0 && pairs > max_block_pairs)
+        return fail(c, SPLAT_ERR_CAPACITY, "the radius brings " + std::to_string(pairs) + " block pairs within reach, max_block_pairs is " +
+                                               std::to_string(max_block_pairs) + "; nothing was written");
+    if (!d_counts) HIP_TRY(c, t.alloc(&d_counts, sizeof(unsigned int) * n));
+    launch_neighbour_counts(c->stream, n, c->planes, c->orig, c->bounds, (const unsigned char*)d_source, r2, cap, d_counts);
+    launch_neighbour_apply(c->stream, n, d_counts, count_min, count_max, op, (unsigned char*)d_selection, d_count);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(&count, d_count, sizeof count, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (count_out) *count_out = count;
     return SPLAT_OK;
 }
 

@@ -367,6 +367,63 @@ class Renderer:
                                                            C.c_void_p(st)))
         return int(count.value)
 
+    block_pairs = None          # what the most recent select_neighbours was bounded by (see there)
+
+    def select_neighbours(self, selection, radius, *, source=None, at_least=0, at_most=None, op="set", counts=None,
+                          max_block_pairs=None, stream=None):
+        """splat_select_neighbours_device: a Gaussian passes when the number of OTHER Gaussians of the source set whose
+        centres lie within `radius` of its own (d2 <= radius^2 in float32, on the resident centres) is in
+        [at_least, at_most]; at_most=None: no upper end.  `selection`, and `op` with what it holds, are select's; `source`
+        is a byte mask like a selection (None: every Gaussian is a source) and may be `selection` itself.  counts: a device
+        buffer of n 32-bit elements that receives the counts (saturated at at_most + 1); selection may then be None.  The
+        two recipes:
+            floaters, fewer than k others within r:   select_neighbours(sel, r, at_most=k-1)
+            grow a selection by r:                    select_neighbours(sel, r, source=sel, at_least=1, op="add")
+        The work is bounded before it is done: the call counts the pairs of 256-Gaussian blocks whose bounds are within reach
+        of each other (kept in self.block_pairs, also when the call is refused) and raises SplatError(ERR_CAPACITY), with
+        nothing written, when they exceed max_block_pairs.  None: 64 per block -- a policy, not a measurement: a radius below
+        a block's own extent reaches a few dozen blocks of a Morton-ordered cloud; 0: no limit.  A scene whose blocks' bounds
+        overlap more than that is refused at ANY radius -- the 1.5 M Gaussian benchmark cloud has 73 pairs per block at
+        radius 0 (profiles/select_neighbours.json): pass a limit there, e.g. 128 * n_blocks.  Returns how many Gaussians are
+        selected after the op (counts only: how many pass)."""
+        radius = float(radius)
+        if not (radius >= 0.0) or radius == float("inf"):
+            raise ValueError("radius: a finite number >= 0 expected, got %r" % (radius,))
+        at_least = int(at_least)
+        at_most = 0xFFFFFFFF if at_most is None else int(at_most)
+        if not (0 <= at_least <= 0xFFFFFFFF and 0 <= at_most <= 0xFFFFFFFF):
+            raise ValueError("at_least / at_most: 32-bit counts expected, got %d and %d" % (at_least, at_most))
+        if at_least > at_most:
+            raise ValueError("at_least (%d) is above at_most (%d): nothing could pass" % (at_least, at_most))
+        if op not in self._SEL_OPS:
+            raise ValueError("op: one of %s, got %r" % (sorted(self._SEL_OPS), op))
+        if selection is None and counts is None:
+            raise ValueError("selection and counts: at least one of the two")
+        dev = int(self.config.device)
+        ps = _byte_mask_address(selection, "selection", self.n, dev) if selection is not None else 0
+        pq = _byte_mask_address(source, "source", self.n, dev) if source is not None else 0
+        pc = 0
+        if counts is not None:
+            if not isinstance(counts, int) and hasattr(counts, "element_size") and int(counts.element_size()) != 4:
+                raise TypeError("counts: 32-bit counts expected, got %s" % getattr(counts, "dtype", None))
+            pc = _device_address(counts, "counts", None, dev, any_dtype=True)
+            if not isinstance(counts, int) and hasattr(counts, "numel") and int(counts.numel()) != self.n:
+                raise ValueError("counts: %d elements expected, got %d" % (self.n, int(counts.numel())))
+        if max_block_pairs is None:
+            max_block_pairs = 64 * ((self.n + 255) // 256)
+        max_block_pairs = int(max_block_pairs)
+        if max_block_pairs < 0:
+            raise ValueError("max_block_pairs: not negative (0: no limit), got %d" % max_block_pairs)
+        st = _producer_stream(stream, (selection, source, counts))
+        count, pairs = C.c_uint64(), C.c_uint64()
+        self.block_pairs = None
+        rc = self._L.splat_select_neighbours_device(self._h, radius, C.c_void_p(pq), at_least, at_most, self._SEL_OPS[op], C.c_void_p(ps),
+                                                    C.c_void_p(pc), max_block_pairs, C.byref(pairs), C.byref(count), C.c_void_p(st))
+        if rc in (_lib.SPLAT_OK, _lib.ERR_CAPACITY):
+            self.block_pairs = int(pairs.value)
+        self._check(rc)
+        return int(count.value)
+
     def compute_cov3d_device(self, scales, rotations, out, stream=None, n=None):
         """splat_compute_cov3d_device: kernel K0 from device buffers (scales [n,3], rotations [n,4]) into a device buffer
         (out [n,9]); arguments and stream as in upload_device.  Returns when `out` is written."""
