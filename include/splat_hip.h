@@ -44,7 +44,7 @@ extern "C" {
  * splat_select_device and splat_selection_indices_device (and the splat_select_query and SPLAT_SEL_* values they take), and
  * splat_read_scene_device, splat_read_gaussians_device, splat_transform_scene_device and splat_transform_gaussians_device, and
  * splat_sh_rotation_blocks, splat_rotate_sh_scene_device and splat_rotate_sh_gaussians_device, and
- * splat_select_neighbours_device. */
+ * splat_select_neighbours_device, and splat_encode_ply_scene_device and splat_encode_ply_gaussians_device. */
 
 /* modes: bit flags, 0 = the default */
 #define SPLAT_MODE_EXACT 0       /* back-to-front, 8-bit truncation per splat as blend() does it; the exponential of
@@ -180,6 +180,36 @@ int splat_decode_ply_device(splat_ctx* ctx, const splat_ply_layout* layout, cons
  * freed and the temporaries are gone.  n == 0: as splat_upload_scene_device with n == 0. */
 int splat_upload_ply_device(splat_ctx* ctx, const splat_ply_layout* layout, const void* d_rows, int32_t compute_cov3d,
                             void* producer_stream);
+/* The way back: the RESIDENT scene written as PLY vertex rows into device memory of the caller -- the inverse of
+ * splat_decode_ply_device, what an editor needs to keep what it did (load, select, edit, save) without a host copy of the
+ * scene.  The scene holds cov3d and an opacity; a row holds three log scales, a quaternion and a logit: every Gaussian's
+ * covariance is decomposed (a double-precision Jacobi iteration, S = V diag(lam) V^T with det V = +1), scale_k =
+ * 0.5 ln(lam_k), (rot_1 rot_2 rot_3 rot_0) = the unit quaternion of V with rot_0 >= 0, opacity = ln(o / (1 - o)).  What
+ * has no logarithm is clamped so that the loader reads back what the scene holds: lam <= 0 (a cov3d left zero, a
+ * rank-deficient matrix) -> scale -104, whose expf is exactly 0; o <= 0 -> -104 (the sigmoid is exactly 0: a Gaussian
+ * deleted by opacity 0 stays deleted); o >= 1 -> +104 (exactly 1); NaN stays NaN; no infinity is written for a finite
+ * opacity.  The arithmetic is splat_amd/csrc/splat_ply_encode_math.h, which calls no libm: the rows are the same bits on
+ * the device and in a host compile of that header.
+ * WHAT A SAVE KEEPS.  Positions and all 48 sh floats keep their bits (pos4's w is no property).  Covariances and opacities
+ * come back through the loader (expf, normalisation, compute_cov3d in f32) NOT bit for bit but within the error of a
+ * float64 eigen-decomposition rounded to f32 the same way (profiles/ply_save_accuracy.json: max |S' - S| / ||S||_F of some
+ * 10-20 units of 2^-24).  load_from_ply subtracts the mean position on every load: a reloaded scene is the saved one
+ * minus its sequential-f32 mean.
+ * The layout is the decoder's: offset[k] = where slot k's float goes in a row, -1 = not written; every byte of a row that
+ * no present slot names (nx ny nz, padding) is written as 0.  Unlike the decoder, the encoder writes whole dwords and
+ * stages every row in LDS -- it has no unstaged path: d_rows_out, stride and every present offset must be multiples of 4,
+ * and stride <= 65528.  Row t is Gaussian t of the scene (layout->n == the resident n), or, indexed, Gaussian d_index[t]
+ * (layout->n == k; u32 original indices in device memory, any order, duplicates allowed, as splat_read_gaussians_device
+ * takes them; producer_stream: where they were written).  Exactly layout->n * stride bytes are written.
+ * SPLAT_ERR_INVALID with the argument named, nothing written, and -- whatever can be judged without it -- before the
+ * context is looked at: a NULL layout, a misaligned d_rows_out, stride or offset, stride == 0 or above 65528, an offset
+ * below -1 or reaching beyond stride, two present offsets that overlap, a NULL d_rows_out or d_index with rows to write,
+ * layout->n that is neither the resident n nor k, an index >= n.  An empty scene and k == 0 succeed and write nothing.
+ * Both are synchronous and READ the scene as splat_read_scene_device does: frames in flight end first, and nothing kept
+ * from frame to frame (retained lists, hints) is lost. */
+int splat_encode_ply_scene_device(splat_ctx* ctx, const splat_ply_layout* layout, void* d_rows_out);
+int splat_encode_ply_gaussians_device(splat_ctx* ctx, uint64_t k, const void* d_index, const splat_ply_layout* layout,
+                                      void* d_rows_out, void* producer_stream);
 
 /* The resident scene edited IN PLACE, n fixed: a training loop that shows its Gaussians every step, an editor that moves,
  * hides or recolours a selection, a player of an animated scene.  Nothing is freed or allocated, nothing is sorted: the

@@ -83,6 +83,17 @@ PlyLayout ply_layout(const std::string& filename);
 // file goes through the host loader and splat_upload_scene.  compute_cov3d == false leaves cov3d zero (Gaussian::new).
 // Returns the number of Gaussians; the frames are those of the host path, byte for byte.
 uint64_t load_ply_to_gpu(splat_ctx* ctx, const std::string& filename, bool compute_cov3d = true);
+// The way back (splat_encode_ply_scene_device, splat_encode_ply_gaussians_device): the RESIDENT scene as PLY vertex rows in
+// device memory -- log scales and a quaternion from cov3d, the logit of the opacity, positions and sh with their bits.
+// d_index == nullptr: the whole scene (layout.n == the resident n); else row t = Gaussian d_index[t] (layout.n == k).  Positions
+// and sh come back bit for bit, covariances and opacities within the error of a float64 decomposition rounded to f32
+// (profiles/ply_save_accuracy.json); the loader recentres on every load.  Throws what the C calls refuse.
+void encode_ply(splat_ctx* ctx, const splat_ply_layout& layout, void* d_rows_out, uint64_t k = 0, const void* d_index = nullptr,
+                void* producer_stream = nullptr);
+splat_ply_layout inria_layout(uint64_t n);      // the canonical 62-float file: 248-byte rows, nx ny nz named by no slot
+// ... and into a file: the canonical header (binary little endian), the rows encoded into a temporary device buffer and
+// copied down once.  d_index == nullptr: the whole scene, k = its n.  Returns the rows written.
+uint64_t save_ply_from_gpu(splat_ctx* ctx, const std::string& filename, uint64_t k, const void* d_index = nullptr);
 // The resident scene edited in place from DEVICE buffers (splat_update_scene_device, splat_update_gaussians_device):
 // `fields` = SPLAT_FIELD_* bits, a buffer whose field is not named may be null.  The whole-field form takes all n rows by
 // original index; the indexed form takes k compact rows, row t for Gaussian d_index[t] (u32, distinct).  The order of the

@@ -135,6 +135,12 @@ extern "C" {
                                    producer_stream: *mut c_void) -> c_int;
     pub fn splat_upload_ply_device(ctx: *mut SplatCtx, layout: *const SplatPlyLayout, d_rows: *const c_void, compute_cov3d: i32,
                                    producer_stream: *mut c_void) -> c_int;
+    // the way back (added under ABI 7, found by symbol like the two above): the resident scene as PLY vertex rows in DEVICE
+    // memory -- log scales and a quaternion from cov3d, the logit of the opacity, positions and sh with their bits; everything
+    // that places a float (d_rows_out, stride, present offsets) a multiple of 4, stride <= 65528; row t = Gaussian t, or d_index[t]
+    pub fn splat_encode_ply_scene_device(ctx: *mut SplatCtx, layout: *const SplatPlyLayout, d_rows_out: *mut c_void) -> c_int;
+    pub fn splat_encode_ply_gaussians_device(ctx: *mut SplatCtx, k: u64, d_index: *const c_void, layout: *const SplatPlyLayout,
+                                             d_rows_out: *mut c_void, producer_stream: *mut c_void) -> c_int;
     // the resident scene edited in place, n fixed (added under ABI 7, found by symbol like the two above): `fields` = SPLAT_FIELD_*
     // bits, a buffer whose field is not named may be null; the indexed form takes k compact rows, row t for Gaussian d_index[t]
     pub fn splat_update_scene_device(ctx: *mut SplatCtx, n: u64, fields: u32, d_pos4: *const c_void, d_cov3d: *const c_void,

@@ -85,6 +85,8 @@ SYMBOLS = [
     ("splat_decode_ply_device", C.c_int, [C.c_void_p, C.POINTER(PlyLayout), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p]),
     ("splat_upload_ply_device", C.c_int, [C.c_void_p, C.POINTER(PlyLayout), C.c_void_p, C.c_int32, C.c_void_p]),
+    ("splat_encode_ply_scene_device", C.c_int, [C.c_void_p, C.POINTER(PlyLayout), C.c_void_p]),
+    ("splat_encode_ply_gaussians_device", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(PlyLayout), C.c_void_p, C.c_void_p]),
     ("splat_update_scene_device", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("splat_update_gaussians_device", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p]),

@@ -13,6 +13,7 @@
 #include <chrono>
 #include <thread>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <sstream>
@@ -339,6 +340,62 @@ uint64_t load_ply_to_gpu(splat_ctx* ctx, const std::string& filename, bool compu
     return pl.layout.n;
 }
 
+void encode_ply(splat_ctx* ctx, const splat_ply_layout& layout, void* d_rows_out, uint64_t k, const void* d_index, void* producer_stream) {
+    if (!ctx) throw std::runtime_error("encode_ply: no context");
+    if (d_index) check(splat_encode_ply_gaussians_device(ctx, k, d_index, &layout, d_rows_out, producer_stream), ctx, "splat_encode_ply_gaussians_device");
+    else check(splat_encode_ply_scene_device(ctx, &layout, d_rows_out), ctx, "splat_encode_ply_scene_device");
+}
+
+namespace {
+// the INRIA property list, in file order: 62 floats
+std::vector<std::string> inria_props() {
+    std::vector<std::string> p = {"x", "y", "z", "nx", "ny", "nz", "f_dc_0", "f_dc_1", "f_dc_2"};
+    for (int i = 0; i < 45; ++i) p.push_back("f_rest_" + std::to_string(i));
+    p.push_back("opacity");
+    for (int i = 0; i < 3; ++i) p.push_back("scale_" + std::to_string(i));
+    for (int i = 0; i < 4; ++i) p.push_back("rot_" + std::to_string(i));
+    return p;
+}
+}  // namespace
+
+splat_ply_layout inria_layout(uint64_t n) {
+    splat_ply_layout l;
+    l.n = n;
+    l.stride = 248;
+    for (int a = 0; a < 3; ++a) l.offset[SPLAT_PLY_SLOT_POS + a] = 4 * a;
+    for (int c = 0; c < 48; ++c) l.offset[SPLAT_PLY_SLOT_SH + c] = c < 3 ? 24 + 4 * c : 36 + 4 * (c - 3);
+    l.offset[SPLAT_PLY_SLOT_OPACITY] = 216;
+    for (int a = 0; a < 3; ++a) l.offset[SPLAT_PLY_SLOT_SCALE + a] = 220 + 4 * a;
+    for (int a = 0; a < 3; ++a) l.offset[SPLAT_PLY_SLOT_ROT + a] = 236 + 4 * a;      // rot_1 rot_2 rot_3
+    l.offset[SPLAT_PLY_SLOT_ROT + 3] = 232;                                            // rot_0 = w
+    return l;
+}
+
+uint64_t save_ply_from_gpu(splat_ctx* ctx, const std::string& filename, uint64_t k, const void* d_index) {
+    if (!ctx) throw std::runtime_error("save_ply_from_gpu: no context");
+    const splat_ply_layout lay = inria_layout(k);
+    const uint64_t bytes = k * (uint64_t)lay.stride;
+    std::vector<unsigned char> rows(bytes);
+    if (k) {
+        void* d_rows = splat_device_alloc(ctx, bytes);
+        if (!d_rows) throw std::runtime_error(std::string("splat_device_alloc: ") + splat_last_error(ctx));
+        int rc = d_index ? splat_encode_ply_gaussians_device(ctx, k, d_index, &lay, d_rows, nullptr) : splat_encode_ply_scene_device(ctx, &lay, d_rows);
+        if (rc == SPLAT_OK) rc = splat_device_download(ctx, rows.data(), d_rows, bytes);
+        splat_device_free(ctx, d_rows);
+        check(rc, ctx, "save_ply_from_gpu");
+    } else {
+        check(splat_encode_ply_scene_device(ctx, &lay, nullptr), ctx, "splat_encode_ply_scene_device");   // (an empty scene, or refused)
+    }
+    std::string head = "ply\nformat binary_little_endian 1.0\nelement vertex " + std::to_string(k) + "\n";
+    for (const std::string& p : inria_props()) head += "property float " + p + "\n";
+    head += "end_header\n";
+    FILE* f = std::fopen(filename.c_str(), "wb");
+    if (!f) throw std::runtime_error("save_ply_from_gpu: cannot open " + filename);
+    const bool ok = std::fwrite(head.data(), 1, head.size(), f) == head.size() && std::fwrite(rows.data(), 1, rows.size(), f) == rows.size();
+    if (std::fclose(f) != 0 || !ok) throw std::runtime_error("save_ply_from_gpu: cannot write " + filename);
+    return k;
+}
+
 void update_scene_device(splat_ctx* ctx, uint64_t n, uint32_t fields, const void* d_pos4, const void* d_cov3d,
                          const void* d_opacity, const void* d_sh, void* producer_stream) {
     if (!ctx) throw std::runtime_error("update_scene_device: no context");
@@ -601,6 +658,18 @@ long long splat_host_load_ply_to_gpu(splat_ctx* ctx, const char* path, int compu
         return -1;
     }
 }
+// save_ply_from_gpu for ctypes: the resident scene (d_index NULL, k = its n) or the Gaussians d_index[0..k) into the canonical
+// INRIA file; returns the rows written, or -1 with the message in err
+long long splat_host_save_ply_from_gpu(splat_ctx* ctx, const char* path, unsigned long long k, const void* d_index, char* err, int errlen) {
+    try {
+        return (long long)splat::save_ply_from_gpu(ctx, path, k, d_index);
+    } catch (const std::exception& e) {
+        if (err && errlen > 0) { std::strncpy(err, e.what(), errlen - 1); err[errlen - 1] = 0; }
+        return -1;
+    }
+}
+// inria_layout for ctypes
+void splat_host_inria_layout(unsigned long long n, splat_ply_layout* out) { if (out) *out = splat::inria_layout(n); }
 void splat_host_cov3d(unsigned long long n, const float* scales3, const float* rot4, float* cov3d) {
     splat::Gaussian g;
     for (unsigned long long i = 0; i < n; ++i) {

@@ -1,5 +1,5 @@
 // splat_internal.h -- shared between the host files (splat_api.hip, splat_scene.hip) and the kernel files (splat_kernels.hip,
-// splat_ply.hip, splat_update.hip, splat_select.hip, splat_neighbours.hip).
+// splat_ply.hip, splat_ply_encode.hip, splat_update.hip, splat_select.hip, splat_neighbours.hip).
 #ifndef SPLAT_INTERNAL_H
 #define SPLAT_INTERNAL_H
 #include <hip/hip_runtime.h>
@@ -174,6 +174,16 @@ void launch_block_bounds(hipStream_t s, uint64_t n, const float* pos4, const flo
 // sequential sum into mean[3] (device, 3 floats), the subtraction.  ev (nullable): four events recorded around the three.
 void launch_ply_decode(hipStream_t s, const splat_ply_layout& lay, const void* d_rows, float* pos4, float* scales3,
                        float* opacity, float* rot4, float* sh, float* mean, hipEvent_t* ev = nullptr);
+// how both PLY kernels stage rows in LDS: a workgroup takes min(PLY_ROWS, PLY_STAGE_BYTES / stride) consecutive rows
+constexpr unsigned int PLY_ROWS = 256;                         // rows per workgroup at most (and threads per workgroup)
+constexpr unsigned int PLY_STAGE_DWORDS = 16384;               // 64 KiB of rows
+constexpr unsigned int PLY_STAGE_BYTES = PLY_STAGE_DWORDS * 4 - 8;   // what a run may hold: <= 3 bytes in front of it, the last dword whole
+// ... and the way back (splat_ply_encode.hip): the resident scene -> PLY vertex rows, row r = Gaussian r (index == nullptr,
+// rows == n) or Gaussian index[r] (checked: launch_index_check), read from slot inv[.] of the planes.  The layout arrives
+// checked: stride a multiple of 4 in [4, PLY_STAGE_BYTES], every present offset a multiple of 4 inside the row, no two equal;
+// d_rows 4-byte aligned.  Bytes of a row that no slot names are written as 0.
+void launch_ply_encode(hipStream_t s, uint64_t n, uint64_t rows, const unsigned int* index, const splat_ply_layout& lay,
+                       const unsigned int* inv, const float4* planes, void* d_rows);
 
 // A resident scene edited in place (splat_update.hip).  `fields`: SPLAT_FIELD_* bits; a buffer whose field is not named is
 // not read.  The order stays: the whole-field form reads row orig[j] for slot j, the indexed form writes slot

@@ -23,10 +23,7 @@ namespace splat {
 // STAGED = false: a row longer than the staging buffer (a stride above 64 KiB) is read from global memory instead,
 // dword by aligned dword in the same way.
 // ---------------------------------------------------------------------------
-constexpr unsigned int PLY_ROWS = 256;                         // rows per workgroup at most (and threads per workgroup)
-constexpr unsigned int PLY_STAGE_DWORDS = 16384;               // 64 KiB of rows
-constexpr unsigned int PLY_STAGE_BYTES = PLY_STAGE_DWORDS * 4 - 8;   // what a run may hold: <= 3 bytes in front of it, the last dword whole
-
+// (PLY_ROWS, PLY_STAGE_DWORDS, PLY_STAGE_BYTES: splat_internal.h -- the encoder stages its rows the same way)
 struct PlyOffsets { int o[SPLAT_PLY_SLOTS]; };                 // by value: kernel arguments, read with constant indices only
 
 // the little-endian float at byte `b` of the dword array `w` (w[0] begins at an aligned address)

@@ -1,7 +1,7 @@
 // splat_scene.hip -- everything that puts values into the resident scene: the uploads (host buffers, device buffers, PLY
 // rows), the in-place edits, K0 (cov3d) and the scene's layout read back -- and the selections read from it, which name the
 // Gaussians such an edit is for.  Host side only, no device code: the kernels are splat_kernels.hip's (order, bounds,
-// packing), splat_ply.hip's, splat_update.hip's, splat_transform.hip's, splat_select.hip's and splat_neighbours.hip's.
+// packing), splat_ply.hip's, splat_ply_encode.hip's, splat_update.hip's, splat_transform.hip's, splat_select.hip's and splat_neighbours.hip's.
 // What the frame scheduler (splat_api.hip) holds per scene is behind the seam of splat_context.h.
 #include <algorithm>
 #include <cmath>
@@ -238,6 +238,33 @@ hipError_t ply_decode_now(splat_ctx* c, const splat_ply_layout& lay, const void*
     HIP_RET(hipStreamSynchronize(c->stream));
     for (int k = 0; k < 3; ++k) { c->ply_ms[k] = 0.0f; (void)hipEventElapsedTime(&c->ply_ms[k], ev[k], ev[k + 1]); }
     return hipSuccess;
+}
+
+// what both PLY encoders refuse before they look at the context or touch HIP (rows: the resident n is judged later, k here);
+// nullptr: nothing.  The kernel owns whole dwords: everything that places a float is a multiple of 4.
+const char* ply_encode_refusal(const splat_ply_layout* lay, const void* d_rows) {
+    if (!lay) return "NULL layout";
+    if ((uintptr_t)d_rows & 3u) return "d_rows_out is misaligned (4 bytes)";
+    if (lay->stride == 0) return "layout->stride is 0";
+    if (lay->stride & 3u) return "layout->stride is not a multiple of 4";
+    if (lay->stride > PLY_STAGE_BYTES) return "layout->stride is above 65528 bytes: a row must fit the encoder's stage";
+    if (lay->n >= 0xFFFFFFFFull) return "layout->n: too many rows (an index is 32-bit)";
+    int present[SPLAT_PLY_SLOTS], m = 0;
+    for (int k = 0; k < SPLAT_PLY_SLOTS; ++k) {
+        const int32_t o = lay->offset[k];
+        if (o < -1) return "layout->offset below -1";
+        if (o < 0) continue;
+        if (o & 3) return "layout->offset is not a multiple of 4";
+        if ((uint64_t)o + 4u > lay->stride) return "layout->offset reaches beyond layout->stride";
+        present[m++] = o;
+    }
+    std::sort(present, present + m);
+    for (int k = 1; k < m; ++k)
+        if (present[k] == present[k - 1]) return "layout->offset: two present properties overlap";
+    if (lay->n && !d_rows) return "NULL d_rows_out";
+    const uint64_t rows = std::min<uint64_t>(PLY_ROWS, PLY_STAGE_BYTES / lay->stride);
+    if ((lay->n + rows - 1) / rows > 0x7FFFFFFFull) return "layout->n: more workgroups than one launch holds";
+    return nullptr;
 }
 }  // namespace
 
@@ -686,6 +713,47 @@ int splat_upload_ply_device(splat_ctx* c, const splat_ply_layout* lay, const voi
     t.release(d_rot);
     guard.armed = false;           // (the upload has a guard of its own)
     return splat_upload_scene_device(c, n, d_pos, d_cov, d_op, d_sh, nullptr);
+}
+
+// The inverses of splat_decode_ply_device: the resident scene as PLY vertex rows in the caller's device buffer.  They READ
+// the scene as splat_read_*_device do -- behind the frames in flight, nothing of a frame's state touched -- and find a row's
+// slot the same way (ensure_inverse).  The arguments are judged before the context is looked at.
+int splat_encode_ply_scene_device(splat_ctx* c, const splat_ply_layout* lay, void* d_rows_out) {
+    if (const char* why = ply_encode_refusal(lay, d_rows_out)) return fail(c, SPLAT_ERR_INVALID, why);
+    if (!c) return fail(c, SPLAT_ERR_INVALID, "NULL context");
+    if (lay->n != c->n) return fail(c, SPLAT_ERR_INVALID, "layout->n is not the resident scene's");
+    if (c->n == 0) return SPLAT_OK;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    int rc = ctx_quiesce(c);
+    if (rc != SPLAT_OK) return rc;
+    HIP_TRY(c, ensure_inverse(c));
+    launch_ply_encode(c->stream, c->n, c->n, nullptr, *lay, c->inv, c->planes, d_rows_out);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SPLAT_OK;
+}
+
+int splat_encode_ply_gaussians_device(splat_ctx* c, uint64_t k, const void* d_index, const splat_ply_layout* lay, void* d_rows_out,
+                                      void* producer_stream) {
+    if (const char* why = ply_encode_refusal(lay, d_rows_out)) return fail(c, SPLAT_ERR_INVALID, why);
+    if (lay->n != k) return fail(c, SPLAT_ERR_INVALID, "layout->n is not k");
+    if (k && !d_index) return fail(c, SPLAT_ERR_INVALID, "NULL d_index");
+    if (!c) return fail(c, SPLAT_ERR_INVALID, "NULL context");
+    if (k == 0) return SPLAT_OK;
+    if (c->n == 0) return fail(c, SPLAT_ERR_NO_SCENE, "no resident scene to encode");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    int rc = ctx_quiesce(c);
+    if (rc != SPLAT_OK) return rc;
+    const unsigned int* index = (const unsigned int*)d_index;
+    HIP_TRY(c, ensure_inverse(c));
+    HIP_TRY(c, follow_producer(c, producer_stream));
+    unsigned int bad = 0;
+    HIP_TRY(c, count_bad_indices(c, k, index, &bad));
+    if (bad) return fail(c, SPLAT_ERR_INVALID, "d_index: an index is not below n; nothing was written");
+    launch_ply_encode(c->stream, c->n, k, index, *lay, c->inv, c->planes, d_rows_out);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SPLAT_OK;
 }
 
 // (debug, not part of the ABI)  Device time of the decode, the sequential sum and the subtraction inside the most recent

@@ -228,6 +228,22 @@ def ply_layout(filename):
     return PlyFileLayout(lay, binary.value, off.value, nbytes.value)
 
 
+def inria_layout(n):
+    """The _lib.PlyLayout of the canonical 62-float INRIA file (PLY_PROPS order, 248-byte rows) for n rows: what
+    Renderer.encode_ply_rows writes a scene into and write_ply / Renderer.save_ply put into a file.  nx ny nz are named by no
+    slot: the encoder writes them as 0."""
+    from . import _lib
+    n = int(n)
+    if n < 0:
+        raise ValueError("inria_layout: n is not negative, got %d" % n)
+    lay = _lib.PlyLayout()
+    lay.n, lay.stride = n, 4 * len(PLY_PROPS)
+    where = {name: 4 * i for i, name in enumerate(PLY_PROPS)}
+    for k, name in enumerate(_lib.PLY_SLOT_NAMES):
+        lay.offset[k] = where[name]
+    return lay
+
+
 def write_ply(filename, raw, n):
     """Write the 62-float INRIA layout (binary little endian).  raw: name -> array; missing -> 0."""
     dt = np.dtype([(p, "<f4") for p in PLY_PROPS])

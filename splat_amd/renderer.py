@@ -495,6 +495,86 @@ class Renderer:
         st = _producer_stream(stream, (rows, positions, scales, opacities, rotations, sh))
         self._check(self._L.splat_decode_ply_device(self._h, C.byref(lay), C.c_void_p(p), *[C.c_void_p(q) for q in ptrs], C.c_void_p(st)))
 
+    def _ply_encode_layout(self, layout):
+        """the layout of an encode, judged as far as Python can: what the kernel needs to own whole dwords"""
+        lay = self._ply_layout_of(layout)
+        if int(lay.stride) == 0 or int(lay.stride) % 4:
+            raise ValueError("layout: stride %d is not a positive multiple of 4" % int(lay.stride))
+        if int(lay.stride) > 65528:
+            raise ValueError("layout: stride %d is above 65528 bytes (a row must fit the encoder's stage)" % int(lay.stride))
+        seen = set()
+        for k, name in enumerate(_lib.PLY_SLOT_NAMES):
+            o = int(lay.offset[k])
+            if o == -1:
+                continue
+            if o < 0 or o % 4 or o + 4 > int(lay.stride):
+                raise ValueError("layout: offset %d of %s is not a multiple of 4 inside the row" % (o, name))
+            if o in seen:
+                raise ValueError("layout: offset %d of %s overlaps another property" % (o, name))
+            seen.add(o)
+        return lay
+
+    def encode_ply_rows(self, rows, layout, index=None, stream=None, k=None):
+        """splat_encode_ply_scene_device / splat_encode_ply_gaussians_device, the inverse of decode_ply_device: the RESIDENT
+        scene written as PLY vertex rows into `rows` (writable device memory of layout.n * layout.stride bytes, 4-byte aligned: a
+        device address or an object with data_ptr()).  layout: gaussians.inria_layout(n), or any _lib.PlyLayout whose stride
+        and present offsets are multiples of 4 (stride <= 65528); offset -1 = not written; bytes no slot names are written
+        as 0.  index=None: row t is Gaussian t (layout.n must be the scene's n); else row t is Gaussian index[t] (uint32 /
+        int32 original indices in device memory, any order, duplicates allowed; k= with a plain address; layout.n must be k).
+        Each covariance becomes three log scales and a unit quaternion (rot_0 >= 0), the opacity its logit; positions and
+        sh keep their bits.  Through the loader the covariances and opacities come back within the error of a float64
+        decomposition rounded to float32, not bit for bit; an opacity of 0 or 1 and a zero covariance come back exactly.
+        Synchronous; reads the scene only, like read_device.  An index >= n raises SplatError(ERR_INVALID), nothing written."""
+        lay = self._ply_encode_layout(layout)
+        if index is None:
+            if int(lay.n) != self.n:
+                raise ValueError("layout: %d rows, the resident scene has %d Gaussians" % (int(lay.n), self.n))
+            p = self._ply_rows(rows, lay) if lay.n else 0
+            if p % 4:
+                raise ValueError("rows: the address is not a multiple of 4")
+            self._check(self._L.splat_encode_ply_scene_device(self._h, C.byref(lay), C.c_void_p(p)))
+            return
+        k, pi = self._index_address(index, k)
+        if int(lay.n) != k:
+            raise ValueError("layout: %d rows for %d indices" % (int(lay.n), k))
+        p = self._ply_rows(rows, lay) if k else 0
+        if p % 4:
+            raise ValueError("rows: the address is not a multiple of 4")
+        st = _producer_stream(stream, (index, rows))
+        self._check(self._L.splat_encode_ply_gaussians_device(self._h, k, C.c_void_p(pi), C.byref(lay), C.c_void_p(p), C.c_void_p(st)))
+
+    def save_ply(self, path, index=None, stream=None, k=None):
+        """The resident scene, or its Gaussians index[0..k) (as in encode_ply_rows), into the canonical 62-float INRIA file at
+        `path` (gaussians.PLY_PROPS order, binary little endian): encoded on the GPU into a temporary device buffer and
+        copied down once (splat_host_save_ply_from_gpu).  What encode_ply_rows says about exactness holds; load_from_ply
+        recentres on every load, so the reloaded positions are the saved ones minus their sequential-float32 mean.  Returns
+        the number of rows written."""
+        import os
+        so = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libsplat_host.so")
+        if not os.path.exists(so):
+            raise RuntimeError("splat_amd: %s is missing -- run __graft_entry__.build()" % so)
+        if index is None:
+            k, pi = self.n, 0
+        else:
+            k, pi = self._index_address(index, k)
+            # the file writer takes no stream: what wrote the indices is waited for here
+            if stream is not None and hasattr(stream, "synchronize"):
+                stream.synchronize()
+            elif stream is not None and int(stream):
+                raise ValueError("save_ply: a raw stream handle cannot be waited for here -- synchronise it and pass stream=None")
+            else:
+                torch = sys.modules.get("torch")
+                if torch is not None and isinstance(index, torch.Tensor):
+                    torch.cuda.current_stream(index.device).synchronize()
+        H = C.CDLL(so)
+        H.splat_host_save_ply_from_gpu.argtypes = [C.c_void_p, C.c_char_p, C.c_ulonglong, C.c_void_p, C.c_char_p, C.c_int]
+        H.splat_host_save_ply_from_gpu.restype = C.c_longlong
+        err = C.create_string_buffer(512)
+        rows = H.splat_host_save_ply_from_gpu(self._h, str(path).encode(), k, C.c_void_p(pi), err, 512)
+        if rows < 0:
+            raise ValueError(err.value.decode("utf-8", "replace") or "save_ply failed")
+        return int(rows)
+
     def scene_layout(self):
         """(orig, bounds) of the current scene: orig[j] = the Gaussian stored in slot j (uint32 [n]); bounds = per K1 block
         of 256 slots lo[3], hi[3], fmax, pad (float32 [ceil(n/256), 8])."""
