@@ -44,7 +44,8 @@ extern "C" {
  * splat_select_device and splat_selection_indices_device (and the splat_select_query and SPLAT_SEL_* values they take), and
  * splat_read_scene_device, splat_read_gaussians_device, splat_transform_scene_device and splat_transform_gaussians_device, and
  * splat_sh_rotation_blocks, splat_rotate_sh_scene_device and splat_rotate_sh_gaussians_device, and
- * splat_select_neighbours_device, and splat_encode_ply_scene_device and splat_encode_ply_gaussians_device. */
+ * splat_select_neighbours_device, and splat_encode_ply_scene_device and splat_encode_ply_gaussians_device, and
+ * splat_pick_device (and the splat_pick_query, splat_pick_result, splat_pick_layer and SPLAT_PICK_* values it takes). */
 
 /* modes: bit flags, 0 = the default */
 #define SPLAT_MODE_EXACT 0       /* back-to-front, 8-bit truncation per splat as blend() does it; the exponential of
@@ -343,6 +344,71 @@ int splat_selection_indices_device(splat_ctx* ctx, uint64_t n, const void* d_sel
 int splat_select_neighbours_device(splat_ctx* ctx, float radius, const void* d_source, uint32_t count_min, uint32_t count_max,
                                    uint32_t op, void* d_selection, void* d_counts_out, uint64_t max_block_pairs,
                                    uint64_t* block_pairs_out, uint64_t* count_out, void* producer_stream);
+/* The PICK: which Gaussian is under a pixel, and what the pixel is made of -- where a click starts.  For up to
+ * SPLAT_PICK_MAX_PIXELS query pixels of the WHOLE target of `cam`, under the context's conventions and its projection (as
+ * splat_select_device sees them: a slab set on the context is ignored), Gaussian i is a HIT of pixel (x, y) when
+ *   - its record r is visible (the SCREEN test's meaning, above) and r.px0 <= x <= r.px1, r.py0 <= y <= r.py1,
+ *   - the reference's fragment() at the sample (sx, sy) = (x + off, y + off), off = 0.5 with sample_half else 0, is accepted:
+ *       dx = sx - r.cx;  dy = y_up ? r.cy - sy : sy - r.cy;  power = -0.5 (A dx dx + C dy dy) - B dx dy   (f32, unfused, A B C = conic)
+ *       rejected when power > 0;  alpha = min(0.99, opacity * expf(power));  rejected when alpha < 1/255,
+ *   - alpha >= alpha_min, and
+ *   - d_mask is NULL or d_mask[i] != 0 (one byte per Gaussian, ORIGINAL index order, exactly like a selection).
+ * The exponential is glibc's expf bit for bit (the one SPLAT_MODE_LIBM_EXP renders with), WHATEVER mode the context renders
+ * in: every alpha reported is the CPU oracle's.  So a frame in SPLAT_MODE_LIBM_EXP accepts exactly the fragments the pick
+ * does; the default mode's exponential can differ from it in the last place and so disagree about a fragment whose alpha
+ * sits on a threshold (1/255, alpha_min).
+ *   Order     The hits of a pixel are ordered NEAREST FIRST -- the reverse of the order the reference draws them in (stable,
+ *             ascending view-space z): descending r.depth and, among equal depths, descending original index.  Float
+ *             comparison: -0.0 and +0.0 are equal.  (A NaN depth is never visible.)
+ *   n_hits    how many hits the pixel has -- exact whatever max_hits is.
+ *   front     the first hit: the Gaussian drawn last.  front_index (SPLAT_PICK_NONE without a hit), front_depth, front_alpha.
+ *   surface   walking the hits nearest first with T_0 = 1, T_k = T_{k-1} * (1 - alpha_k) in f32 (the subtraction rounded,
+ *             then the product, unfused) and coverage_k = 1 - T_k, the surface is the first hit with coverage_k >=
+ *             coverage_min: surface_index, surface_depth and that coverage.  When no hit reaches coverage_min,
+ *             surface_index = SPLAT_PICK_NONE, surface_depth = 0 and surface_coverage is the coverage after the last hit (0
+ *             without a hit).  This is what a click should select: a faint floater in front of a wall does not win.  It is
+ *             FLOAT transmittance, not the reference's blend, which truncates the pixel to 8 bits after every Gaussian.
+ *   layers    with max_layers > 0: the first min(n_hits, max_layers) hits of pixel p in order, at d_layers[p * max_layers ..],
+ *             each {index, depth, alpha, coverage_k}.  The rows behind them are left as they are.
+ *   max_hits  bounds the list the library keeps per pixel (1 <= max_hits <= SPLAT_PICK_MAX_HITS).  A pixel with MORE hits gets
+ *             flags |= SPLAT_PICK_TRUNCATED: n_hits and the front are still exact, surface_index = SPLAT_PICK_NONE,
+ *             surface_depth = surface_coverage = 0 and none of its layer rows is written.  The other pixels of the call are
+ *             unaffected and the call returns SPLAT_OK.  (The 1.5 M Gaussian benchmark cloud has about 2 000 hits on the pixels of
+ *             its middle: profiles/pick.json.)
+ * pixels_xy: n_pixels (x, y) pairs in HOST memory (they come from the mouse); duplicates are fine.  d_results (n_pixels
+ * splat_pick_result) and d_layers are the caller's DEVICE memory, 4-byte aligned, so that pick -> indices -> edit stays on the
+ * GPU.  Stream, event and synchronisation semantics are splat_select_device's: synchronous, ordered on the context's stream
+ * behind the frames in flight (producer_stream: the stream that wrote d_mask), and it READS the scene: the state kept from
+ * frame to frame, retained lists included, survives, and splat_device_bytes() is as before -- the one temporary (20 bytes per
+ * pixel and 12 per pixel and hit of max_hits: 12 MB at the most) lives for the call.
+ * SPLAT_ERR_INVALID, judged before the context is looked at, nothing written, splat_last_error names the argument: a NULL q or
+ * cam, a target that is no integer size in [1, 65535], n_pixels > SPLAT_PICK_MAX_PIXELS, a NULL pixels_xy or d_results with
+ * n_pixels > 0, a pixel outside [0, w) x [0, h), max_hits outside [1, SPLAT_PICK_MAX_HITS], max_layers > max_hits,
+ * coverage_min not in (0, 1] (a NaN among it), a NaN alpha_min, max_layers > 0 with a NULL d_layers, a misaligned d_results
+ * or d_layers.  Then a NULL context: SPLAT_ERR_INVALID; n_pixels == 0: SPLAT_OK, nothing done; no resident scene:
+ * SPLAT_ERR_NO_SCENE.  The multi-GPU layer needs no counterpart, as for splat_select_device. */
+#define SPLAT_PICK_MAX_PIXELS 256
+#define SPLAT_PICK_MAX_HITS   4096
+#define SPLAT_PICK_NONE       0xFFFFFFFFu
+#define SPLAT_PICK_TRUNCATED  1u
+typedef struct {
+    float    alpha_min;        /* a hit's alpha is at least this; 0 = every accepted fragment */
+    float    coverage_min;     /* the surface is the first hit whose coverage reaches this; in (0, 1] */
+    uint32_t max_hits;         /* the list kept per pixel: 1 .. SPLAT_PICK_MAX_HITS */
+    uint32_t max_layers;       /* layer rows per pixel in d_layers; 0 = none; <= max_hits */
+} splat_pick_query;
+typedef struct {
+    uint32_t n_hits, flags, front_index;
+    float    front_depth, front_alpha;
+    uint32_t surface_index;
+    float    surface_depth, surface_coverage;
+} splat_pick_result;
+typedef struct {
+    uint32_t index;
+    float    depth, alpha, coverage;
+} splat_pick_layer;
+int splat_pick_device(splat_ctx* ctx, const splat_pick_query* q, const splat_camera* cam, uint32_t n_pixels,
+                      const int32_t* pixels_xy, const void* d_mask, void* d_results, void* d_layers, void* producer_stream);
 
 /* The resident values GIVEN BACK, and changed WHERE THEY LIE: with these two an editor that moves, rotates or scales a
  * selection keeps no copy of the scene (after an upload from PLY rows it never had one), and select -> indices -> transform,

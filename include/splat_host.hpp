@@ -130,6 +130,13 @@ void rotate_sh_gaussians_device(splat_ctx* ctx, uint64_t k, const void* d_index,
 uint64_t select_neighbours(splat_ctx* ctx, float radius, const void* d_source, uint32_t count_min, uint32_t count_max, uint32_t op,
                            void* d_selection, void* d_counts_out, uint64_t max_block_pairs, uint64_t* block_pairs_out = nullptr,
                            void* producer_stream = nullptr);
+// What lies under up to SPLAT_PICK_MAX_PIXELS pixels of the target of cam (splat_pick_device): pixels_xy = n_pixels (x, y) pairs in
+// host memory; per pixel a splat_pick_result into d_results -- n_hits, the front hit and the surface, the first hit nearest
+// first at which the float coverage reaches q.coverage_min: what a click should select -- and, with q.max_layers > 0,
+// q.max_layers splat_pick_layer rows into d_layers (both device memory).  d_mask: one byte per Gaussian like a selection, null =
+// all.  Throws what the C call refuses.
+void pick(splat_ctx* ctx, const splat_pick_query& q, const splat_camera& cam, uint32_t n_pixels, const int32_t* pixels_xy,
+          const void* d_mask, void* d_results, void* d_layers = nullptr, void* producer_stream = nullptr);
 
 struct GaussianList {           // src/gaussians.rs:408-416, SoA
     std::vector<float> positions;   // 4 x N (x,y,z,1)

@@ -92,6 +92,31 @@ pub struct SplatPlyLayout {
     pub n: u64, pub stride: u32, pub offset: [i32; SPLAT_PLY_SLOTS],
 }
 
+// the pick: its limits, the index of "none", the one flag of a result, and the three layouts (16, 32 and 16 bytes)
+pub const SPLAT_PICK_MAX_PIXELS: u32 = 256;
+pub const SPLAT_PICK_MAX_HITS: u32 = 4096;
+pub const SPLAT_PICK_NONE: u32 = 0xFFFF_FFFF;
+pub const SPLAT_PICK_TRUNCATED: u32 = 1;
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct SplatPickQuery {
+    pub alpha_min: f32,                            // a hit's alpha is at least this
+    pub coverage_min: f32,                         // the surface: the first hit whose coverage reaches this; in (0, 1]
+    pub max_hits: u32,                             // the list kept per pixel: 1 ..= SPLAT_PICK_MAX_HITS
+    pub max_layers: u32,                           // layer rows per pixel; 0 = none; <= max_hits
+}
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct SplatPickResult {
+    pub n_hits: u32, pub flags: u32, pub front_index: u32,
+    pub front_depth: f32, pub front_alpha: f32,
+    pub surface_index: u32,
+    pub surface_depth: f32, pub surface_coverage: f32,
+}
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct SplatPickLayer {
+    pub index: u32,
+    pub depth: f32, pub alpha: f32, pub coverage: f32,
+}
+
 // a selection query: a Gaussian passes when every test named in `tests` (SPLAT_SEL_* bits) passes; 0 = all pass
 #[repr(C)] #[derive(Clone, Copy, Default)]
 pub struct SplatSelectQuery {
@@ -163,6 +188,13 @@ extern "C" {
     pub fn splat_select_neighbours_device(ctx: *mut SplatCtx, radius: f32, d_source: *const c_void, count_min: u32, count_max: u32,
                                           op: u32, d_selection: *mut c_void, d_counts_out: *mut c_void, max_block_pairs: u64,
                                           block_pairs_out: *mut u64, count_out: *mut u64, producer_stream: *mut c_void) -> c_int;
+    // ... and the pick (added under ABI 7, found by symbol): the Gaussians whose fragment the reference accepts at up to
+    // SPLAT_PICK_MAX_PIXELS pixels of the target of cam (pixels_xy: n_pixels (x, y) pairs in HOST memory), nearest first; per pixel
+    // a SplatPickResult into d_results and, with max_layers > 0, max_layers SplatPickLayer rows into d_layers (device memory;
+    // d_layers may be null when max_layers == 0); d_mask: one byte per Gaussian like a selection, null = all
+    pub fn splat_pick_device(ctx: *mut SplatCtx, q: *const SplatPickQuery, cam: *const SplatCamera, n_pixels: u32,
+                             pixels_xy: *const i32, d_mask: *const c_void, d_results: *mut c_void, d_layers: *mut c_void,
+                             producer_stream: *mut c_void) -> c_int;
     // the resident values given back, and mapped where they lie (added under ABI 7, found by symbol like those above): the reads
     // are the updates' inverses (same layouts and SPLAT_FIELD_* bits; pos4 gets w = 1; a buffer whose field is not named may be
     // null and is left untouched) and read the scene as a selection does; m = 3x4 row-major affine map in HOST memory, applied

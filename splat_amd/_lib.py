@@ -56,6 +56,26 @@ class SelectQuery(C.Structure):
                 ("depth_min", C.c_float), ("depth_max", C.c_float), ("opacity_min", C.c_float), ("opacity_max", C.c_float)]
 
 
+# splat_pick_device: its limits, the index of "none" and the one flag of a result
+PICK_MAX_PIXELS, PICK_MAX_HITS, PICK_NONE, PICK_TRUNCATED = 256, 4096, 0xFFFFFFFF, 1
+
+
+class PickQuery(C.Structure):
+    """splat_pick_query"""
+    _fields_ = [("alpha_min", C.c_float), ("coverage_min", C.c_float), ("max_hits", C.c_uint32), ("max_layers", C.c_uint32)]
+
+
+class PickResult(C.Structure):
+    """splat_pick_result: one per query pixel"""
+    _fields_ = [("n_hits", C.c_uint32), ("flags", C.c_uint32), ("front_index", C.c_uint32), ("front_depth", C.c_float),
+                ("front_alpha", C.c_float), ("surface_index", C.c_uint32), ("surface_depth", C.c_float), ("surface_coverage", C.c_float)]
+
+
+class PickLayer(C.Structure):
+    """splat_pick_layer: one per query pixel and layer"""
+    _fields_ = [("index", C.c_uint32), ("depth", C.c_float), ("alpha", C.c_float), ("coverage", C.c_float)]
+
+
 PLY_SLOTS = 59
 # destination slots of splat_ply_layout.offset: (first slot, count) per buffer, and the PLY property that feeds each slot
 PLY_SLOT_POS, PLY_SLOT_SCALE, PLY_SLOT_OPACITY, PLY_SLOT_ROT, PLY_SLOT_SH = 0, 3, 6, 7, 11
@@ -96,6 +116,8 @@ SYMBOLS = [
                                                  C.c_void_p]),
     ("splat_select_neighbours_device", C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
                                                  C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]),
+    ("splat_pick_device", C.c_int, [C.c_void_p, C.POINTER(PickQuery), C.POINTER(CameraC), C.c_uint32, C.POINTER(C.c_int32), C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     ("splat_read_scene_device", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("splat_read_gaussians_device", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p]),

@@ -456,6 +456,12 @@ uint64_t select_neighbours(splat_ctx* ctx, float radius, const void* d_source, u
     return count;
 }
 
+void pick(splat_ctx* ctx, const splat_pick_query& q, const splat_camera& cam, uint32_t n_pixels, const int32_t* pixels_xy,
+          const void* d_mask, void* d_results, void* d_layers, void* producer_stream) {
+    if (!ctx) throw std::runtime_error("pick: no context");
+    check(splat_pick_device(ctx, &q, &cam, n_pixels, pixels_xy, d_mask, d_results, d_layers, producer_stream), ctx, "splat_pick_device");
+}
+
 // load_from_ply (src/gaussians.rs:375-405): the AoS `Vec<Gaussian>` the reference returns, from the same decode
 std::vector<Gaussian> load_from_ply(const std::string& filename) {
     GaussianList l = load_from_ply_soa(filename, 0);

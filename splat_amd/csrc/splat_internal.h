@@ -1,5 +1,5 @@
 // splat_internal.h -- shared between the host files (splat_api.hip, splat_scene.hip) and the kernel files (splat_kernels.hip,
-// splat_ply.hip, splat_ply_encode.hip, splat_update.hip, splat_select.hip, splat_neighbours.hip).
+// splat_ply.hip, splat_ply_encode.hip, splat_update.hip, splat_select.hip, splat_neighbours.hip, splat_pick.hip).
 #ifndef SPLAT_INTERNAL_H
 #define SPLAT_INTERNAL_H
 #include <hip/hip_runtime.h>
@@ -252,6 +252,22 @@ void launch_neighbour_counts(hipStream_t s, uint64_t n, const float4* planes, co
                              const unsigned char* source, float r2, unsigned int cap, unsigned int* counts);
 void launch_neighbour_apply(hipStream_t s, uint64_t n, const unsigned int* counts, unsigned int count_min, unsigned int count_max,
                             uint32_t op, unsigned char* selection, unsigned int* count);
+// ... and what a pixel is made of (splat_pick.hip).  The query arrives checked; pixels: n_pixels (x, y) pairs in DEVICE memory,
+// all on the target, bound: (x0, y0, x1, y1) of all of them; mask: one byte per Gaussian, ORIGINAL index order, or nullptr.
+// PickTemps: the call's temporaries -- counts and fronts: n_pixels words each, ZEROED by the caller; list_key and list_alpha:
+// n_pixels * max_hits entries each, pixel q's at q * max_hits.  results: n_pixels splat_pick_result; layers: n_pixels *
+// max_layers splat_pick_layer (not read when max_layers == 0).  Three launches, each reading what those before it wrote.
+constexpr unsigned int PICK_MAX_PIXELS = 256;   // SPLAT_PICK_MAX_PIXELS: the queries fit one workgroup's LDS stage
+constexpr unsigned int PICK_MAX_HITS = 4096;    // SPLAT_PICK_MAX_HITS: a pixel's list fits one workgroup's LDS (48 KB)
+struct PickTemps {
+    unsigned int* counts;
+    unsigned long long* fronts;
+    unsigned long long* list_key;
+    float* list_alpha;
+};
+void launch_pick(hipStream_t s, uint64_t n, const float4* planes, const unsigned int* orig, const unsigned char* mask, const SelectView& v,
+                 const splat_pick_query& q, unsigned int n_pixels, const int2* pixels, int4 bound, const PickTemps& t, void* results,
+                 void* layers);
 
 // ---- The per-frame launches take one argument block each, by const&.  The blocks are plain aggregates without defaults: a
 // caller value-initialises one (`ScanArgs a{};`) and what it does not set is zero / nullptr / false.  What travels together

@@ -1,7 +1,7 @@
 // splat_scene.hip -- everything that puts values into the resident scene: the uploads (host buffers, device buffers, PLY
 // rows), the in-place edits, K0 (cov3d) and the scene's layout read back -- and the selections read from it, which name the
 // Gaussians such an edit is for.  Host side only, no device code: the kernels are splat_kernels.hip's (order, bounds,
-// packing), splat_ply.hip's, splat_ply_encode.hip's, splat_update.hip's, splat_transform.hip's, splat_select.hip's and splat_neighbours.hip's.
+// packing), splat_ply.hip's, splat_ply_encode.hip's, splat_update.hip's, splat_transform.hip's, splat_select.hip's, splat_neighbours.hip's and splat_pick.hip's.
 // What the frame scheduler (splat_api.hip) holds per scene is behind the seam of splat_context.h.
 #include <algorithm>
 #include <cmath>
@@ -184,6 +184,19 @@ hipError_t count_bad_indices(splat_ctx* c, uint64_t k, const unsigned int* index
     return hipStreamSynchronize(c->stream);
 }
 
+// the camera (nullable) and the context's conventions as the scene queries' kernels take them; W and H are the caller's to set
+SelectView select_view(const splat_ctx* c, const splat_camera* cam) {
+    SelectView v{};
+    if (cam) {
+        std::copy(cam->view, cam->view + 16, v.view);
+        std::copy(cam->proj, cam->proj + 16, v.proj);
+        v.w = cam->w; v.h = cam->h; v.htanx = cam->htanx; v.htany = cam->htany; v.focal = cam->focal; v.lowpass = cam->lowpass;
+    }
+    v.y_up = c->cfg.y_up; v.sample_half = c->cfg.sample_half; v.zclip = c->cfg.zclip; v.zmin = c->cfg.zmin; v.zmax = c->cfg.zmax;
+    v.corrected = (c->cfg.mode & SPLAT_MODE_CORRECTED_PROJECTION) ? 1 : 0;
+    return v;
+}
+
 // what splat_select_device refuses before it looks at the context or touches HIP; nullptr: nothing
 constexpr uint32_t SEL_TESTS_ALL = SPLAT_SEL_VOLUME | SPLAT_SEL_SCREEN | SPLAT_SEL_DEPTH | SPLAT_SEL_OPACITY;
 const char* select_refusal(const splat_select_query* q, const splat_camera* cam, const void* pixel_mask, uint32_t op) {
@@ -209,6 +222,30 @@ const char* neighbours_refusal(float radius, uint32_t count_min, uint32_t count_
     if (op > SPLAT_SEL_OP_INTERSECT) return "unknown op";
     if (!selection && !counts_out) return "d_selection and d_counts_out are both NULL";
     if ((uintptr_t)counts_out & 3u) return "d_counts_out is misaligned (4 bytes)";
+    return nullptr;
+}
+
+// what splat_pick_device refuses before it looks at the context or touches HIP; nullptr: nothing
+const char* pick_refusal(const splat_pick_query* q, const splat_camera* cam, uint32_t n_pixels, const int32_t* pixels_xy,
+                         const void* results, const void* layers) {
+    if (!q) return "NULL q";
+    if (!cam) return "NULL cam";
+    if (!(cam->w >= 1.0f) || !(cam->h >= 1.0f) || cam->w > 65535.0f || cam->h > 65535.0f || cam->w != std::floor(cam->w) ||
+        cam->h != std::floor(cam->h))
+        return "cam: w/h must be integers in [1, 65535]";
+    if (n_pixels > SPLAT_PICK_MAX_PIXELS) return "n_pixels is above SPLAT_PICK_MAX_PIXELS (256)";
+    if (q->max_hits < 1u || q->max_hits > SPLAT_PICK_MAX_HITS) return "max_hits is outside [1, SPLAT_PICK_MAX_HITS (4096)]";
+    if (q->max_layers > q->max_hits) return "max_layers is above max_hits";
+    if (!(q->coverage_min > 0.0f) || !(q->coverage_min <= 1.0f)) return "coverage_min is not in (0, 1]";
+    if (q->alpha_min != q->alpha_min) return "alpha_min is NaN";
+    if (q->max_layers > 0u && !layers) return "NULL d_layers with max_layers > 0";
+    if (((uintptr_t)results | (uintptr_t)layers) & 3u) return "d_results or d_layers is misaligned (4 bytes)";
+    if (n_pixels && !pixels_xy) return "NULL pixels_xy";
+    if (n_pixels && !results) return "NULL d_results";
+    const int W = (int)cam->w, H = (int)cam->h;
+    for (uint32_t p = 0; p < n_pixels; ++p)
+        if (pixels_xy[2 * p] < 0 || pixels_xy[2 * p] >= W || pixels_xy[2 * p + 1] < 0 || pixels_xy[2 * p + 1] >= H)
+            return "pixels_xy: a pixel lies outside [0, w) x [0, h)";
     return nullptr;
 }
 
@@ -569,14 +606,7 @@ int splat_select_device(splat_ctx* c, const splat_select_query* q, const splat_c
     int rc = ctx_quiesce(c);
     if (rc != SPLAT_OK) return rc;
     splat_select_query k = *q;
-    SelectView v{};
-    if (cam) {
-        std::copy(cam->view, cam->view + 16, v.view);
-        std::copy(cam->proj, cam->proj + 16, v.proj);
-        v.w = cam->w; v.h = cam->h; v.htanx = cam->htanx; v.htany = cam->htany; v.focal = cam->focal; v.lowpass = cam->lowpass;
-    }
-    v.y_up = c->cfg.y_up; v.sample_half = c->cfg.sample_half; v.zclip = c->cfg.zclip; v.zmin = c->cfg.zmin; v.zmax = c->cfg.zmax;
-    v.corrected = (c->cfg.mode & SPLAT_MODE_CORRECTED_PROJECTION) ? 1 : 0;
+    SelectView v = select_view(c, cam);
     if (k.tests & SPLAT_SEL_SCREEN) {
         v.W = (int)cam->w; v.H = (int)cam->h;
         k.x0 = std::max(k.x0, 0); k.y0 = std::max(k.y0, 0);
@@ -661,6 +691,49 @@ int splat_select_neighbours_device(splat_ctx* c, float radius, const void* d_sou
     HIP_TRY(c, hipMemcpyAsync(&count, d_count, sizeof count, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (count_out) *count_out = count;
+    return SPLAT_OK;
+}
+
+// The pick reads the scene as the selections do, on the whole target.  What it allocates goes with the call: one buffer that
+// holds the pixels, a counter and a front key per pixel, and a list of max_hits entries per pixel.
+int splat_pick_device(splat_ctx* c, const splat_pick_query* q, const splat_camera* cam, uint32_t n_pixels, const int32_t* pixels_xy,
+                      const void* d_mask, void* d_results, void* d_layers, void* producer_stream) {
+    // (the arguments are judged before the context is looked at, as the PLY entry points do it)
+    if (const char* why = pick_refusal(q, cam, n_pixels, pixels_xy, d_results, d_layers)) return fail(c, SPLAT_ERR_INVALID, why);
+    if (!c) return fail(c, SPLAT_ERR_INVALID, "NULL context");
+    if (n_pixels == 0) return SPLAT_OK;
+    if (c->n == 0) return fail(c, SPLAT_ERR_NO_SCENE, "no resident scene to pick from");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    int rc = ctx_quiesce(c);
+    if (rc != SPLAT_OK) return rc;
+    SelectView v = select_view(c, cam);
+    v.W = (int)cam->w; v.H = (int)cam->h;
+    int4 bound = make_int4(v.W, v.H, -1, -1);                   // x0 y0 x1 y1 of all the queries
+    for (uint32_t p = 0; p < n_pixels; ++p) {
+        bound.x = std::min(bound.x, pixels_xy[2 * p]); bound.z = std::max(bound.z, pixels_xy[2 * p]);
+        bound.y = std::min(bound.y, pixels_xy[2 * p + 1]); bound.w = std::max(bound.w, pixels_xy[2 * p + 1]);
+    }
+    // one temporary: per pixel a front key and a list of max_hits keys (8 bytes each), then the pixels themselves (8), then a
+    // counter and the list's alphas (4 each); the front keys and the counters are zeroed
+    const size_t np_ = n_pixels, mh = q->max_hits;
+    const size_t keys_bytes = 8u * np_ * (1u + mh), words_bytes = 4u * np_ * (1u + mh);
+    Temps t(c);
+    unsigned char* d_tmp = nullptr;
+    static_assert(sizeof(int2) == 8, "the pixels keep the 8-byte alignment of what lies before them");
+    HIP_TRY(c, t.alloc(&d_tmp, keys_bytes + sizeof(int2) * np_ + words_bytes));
+    PickTemps pt{};
+    pt.fronts = (unsigned long long*)d_tmp;
+    pt.list_key = pt.fronts + np_;
+    int2* const d_pixels = (int2*)(d_tmp + keys_bytes);
+    pt.counts = (unsigned int*)(d_tmp + keys_bytes + sizeof(int2) * np_);
+    pt.list_alpha = (float*)(pt.counts + np_);
+    HIP_TRY(c, hipMemcpyAsync(d_pixels, pixels_xy, sizeof(int2) * np_, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(pt.fronts, 0, 8u * np_, c->stream));
+    HIP_TRY(c, hipMemsetAsync(pt.counts, 0, 4u * np_, c->stream));
+    HIP_TRY(c, follow_producer(c, producer_stream));
+    launch_pick(c->stream, c->n, c->planes, c->orig, (const unsigned char*)d_mask, v, *q, n_pixels, d_pixels, bound, pt, d_results, d_layers);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     return SPLAT_OK;
 }
 

@@ -424,6 +424,69 @@ class Renderer:
         self._check(rc)
         return int(count.value)
 
+    # the layouts of splat_pick_result and splat_pick_layer, as numpy sees them
+    PICK_RESULT_DTYPE = np.dtype([("n_hits", "u4"), ("flags", "u4"), ("front_index", "u4"), ("front_depth", "f4"), ("front_alpha", "f4"),
+                                  ("surface_index", "u4"), ("surface_depth", "f4"), ("surface_coverage", "f4")])
+    PICK_LAYER_DTYPE = np.dtype([("index", "u4"), ("depth", "f4"), ("alpha", "f4"), ("coverage", "f4")])
+
+    def pick(self, cam_c, pixels, *, alpha_min=0.0, coverage=0.5, mask=None, max_hits=1024, layers=0, results=None, layers_out=None,
+             stream=None):
+        """splat_pick_device: what lies under the pixels -- (x, y) pairs of the target of cam_c, AT MOST 256 of them: more
+        raises ValueError (split the call; nothing loops silently).  A Gaussian is a hit of a pixel when the reference's
+        fragment of it is accepted there with alpha >= alpha_min (glibc's expf, whatever mode the context renders in) and
+        its byte in `mask` (a selection: n bytes of device memory; None: all) is nonzero.  Hits are ordered nearest first.
+        Per pixel: n_hits, flags, the front hit (front_index, front_depth, front_alpha) and the surface -- the first hit at
+        which the float coverage 1 - prod(1 - alpha) reaches `coverage` (surface_index, surface_depth, surface_coverage;
+        index 0xFFFFFFFF when none does) -- which is what a click should select.  layers=k: also the first k hits of every
+        pixel, each (index, depth, alpha, coverage).  max_hits (1..4096) bounds the list kept per pixel: a pixel with more
+        hits has flags & 1 set, exact n_hits and front, no surface and no layers.
+        Returns a numpy structured array of len(pixels) results (PICK_RESULT_DTYPE), or with layers=k the pair (results,
+        layers [len(pixels), k] of PICK_LAYER_DTYPE; rows beyond a pixel's hits are zero).  With results= (and layers_out=
+        when layers > 0) -- device tensors or addresses of 32 bytes per pixel and 16 per pixel and layer -- the call
+        writes there, copies nothing down and returns None: pick -> indices -> edit stays on the GPU."""
+        px = np.ascontiguousarray(pixels, np.int32).reshape(-1, 2)
+        if len(px) > _lib.PICK_MAX_PIXELS:
+            raise ValueError("pixels: at most %d per call, got %d" % (_lib.PICK_MAX_PIXELS, len(px)))
+        max_hits, layers = int(max_hits), int(layers)
+        if not 1 <= max_hits <= _lib.PICK_MAX_HITS:
+            raise ValueError("max_hits: 1 .. %d expected, got %d" % (_lib.PICK_MAX_HITS, max_hits))
+        if not 0 <= layers <= max_hits:
+            raise ValueError("layers: 0 .. max_hits (%d) expected, got %d" % (max_hits, layers))
+        if (results is None) != (layers_out is None) and layers > 0:
+            raise ValueError("results= and layers_out=: both or neither when layers > 0")
+        q = _lib.PickQuery(float(alpha_min), float(coverage), max_hits, layers)
+        dev = int(self.config.device)
+        pm = _byte_mask_address(mask, "mask", self.n, dev) if mask is not None else 0
+        st = _producer_stream(stream, (mask, results, layers_out))
+        k = len(px)
+        own = results is None
+        if own:                               # one buffer of the call's own: the results, the layer rows behind them
+            pr = self._L.splat_device_alloc(self._h, max(32 * k + 16 * k * layers, 4))
+            if not pr:
+                raise SplatError(_lib.ERR_HIP, (self._L.splat_last_error(self._h) or b"pick: no device memory for the results").decode())
+            pl = pr + 32 * k
+        else:
+            pr = _device_address(results, "results", None, dev, any_dtype=True)
+            pl = _device_address(layers_out, "layers_out", None, dev, any_dtype=True) if layers_out is not None else 0
+        try:
+            self._check(self._L.splat_pick_device(self._h, C.byref(q), C.byref(cam_c), k, px.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                  C.c_void_p(pm), C.c_void_p(pr), C.c_void_p(pl) if layers else None, C.c_void_p(st)))
+            if not own:
+                return None
+            raw = np.zeros(32 * k + 16 * k * layers, np.uint8)
+            if raw.nbytes:
+                self._check(self._L.splat_device_download(self._h, C.c_void_p(raw.ctypes.data), C.c_void_p(pr), raw.nbytes))
+            res = raw[:32 * k].view(self.PICK_RESULT_DTYPE).copy()
+            if not layers:
+                return res
+            lay = raw[32 * k:].view(self.PICK_LAYER_DTYPE).reshape(k, layers).copy()
+            due = np.where(res["flags"] & _lib.PICK_TRUNCATED, 0, np.minimum(res["n_hits"], layers))
+            lay[np.arange(layers)[None, :] >= due[:, None]] = np.zeros((), self.PICK_LAYER_DTYPE)   # the library leaves those rows alone
+            return res, lay
+        finally:
+            if own:
+                self.device_free(pr)
+
     def compute_cov3d_device(self, scales, rotations, out, stream=None, n=None):
         """splat_compute_cov3d_device: kernel K0 from device buffers (scales [n,3], rotations [n,4]) into a device buffer
         (out [n,9]); arguments and stream as in upload_device.  Returns when `out` is written."""
