@@ -45,7 +45,8 @@ extern "C" {
  * splat_read_scene_device, splat_read_gaussians_device, splat_transform_scene_device and splat_transform_gaussians_device, and
  * splat_sh_rotation_blocks, splat_rotate_sh_scene_device and splat_rotate_sh_gaussians_device, and
  * splat_select_neighbours_device, and splat_encode_ply_scene_device and splat_encode_ply_gaussians_device, and
- * splat_pick_device (and the splat_pick_query, splat_pick_result, splat_pick_layer and SPLAT_PICK_* values it takes). */
+ * splat_pick_device (and the splat_pick_query, splat_pick_result, splat_pick_layer and SPLAT_PICK_* values it takes), and
+ * splat_remove_gaussians_device (and the SPLAT_REMOVE_* values it takes). */
 
 /* modes: bit flags, 0 = the default */
 #define SPLAT_MODE_EXACT 0       /* back-to-front, 8-bit truncation per splat as blend() does it; the exponential of
@@ -409,6 +410,36 @@ typedef struct {
 } splat_pick_layer;
 int splat_pick_device(splat_ctx* ctx, const splat_pick_query* q, const splat_camera* cam, uint32_t n_pixels,
                       const int32_t* pixels_xy, const void* d_mask, void* d_results, void* d_layers, void* producer_stream);
+
+/* Gaussians TAKEN OUT of the resident scene -- delete what is selected, or crop to it -- with the survivors compacted where
+ * they lie: nothing crosses PCIe but one count, nothing is sorted (the survivors of a Morton-ordered scene are Morton-ordered),
+ * and the memory of what went is given back.  `mode`: */
+#define SPLAT_REMOVE_SELECTED   0u   /* the selected Gaussians go (delete) */
+#define SPLAT_REMOVE_UNSELECTED 1u   /* the selected Gaussians stay (crop) */
+/* d_selection: as splat_select_device writes it -- n bytes of device memory at any byte address, ORIGINAL index order,
+ * nonzero = selected; n must be the resident scene's.  *n_out (required) = the survivors n'.  Survivors keep their relative
+ * original order: the new index of one is its rank among the survivors in original index order, and from the call on every
+ * index, row and selection byte the library takes or gives means the new numbering.  d_index_map_out (nullable; n u32,
+ * 4-byte aligned): entry i = the new index of old Gaussian i, or 0xFFFFFFFF if it went -- what carries the caller's own
+ * per-Gaussian arrays and other selections across the call.  Synchronous; producer_stream as for splat_update_*_device.
+ *   n' == n   nothing went: SPLAT_OK, the identity map if asked for, and the call has READ the scene as a selection does --
+ *             region layouts, hints, retained lists and the inverse order all survive.
+ *   n' == 0   the context is as splat_upload_scene(n = 0) leaves it.
+ *   else      an edit that also changes n: frames queued before it show the scene as it was (one found skipped stays pending
+ *             for splat_sync), afterwards the context is what an upload of the survivors makes of it -- the state kept from
+ *             frame to frame starts over, the inverse order is made again on first use -- except that the scene's order is
+ *             the old one's without the slots that went (splat_get_scene_layout), not a new sort's.  The frames that follow
+ *             are those of a fresh splat_upload_scene of the survivors, byte for byte.  splat_device_bytes() is what it is
+ *             after uploading the survivors over the old scene; during the call the old scene and the new planes (256 B per
+ *             survivor) exist side by side.  If those cannot be allocated: SPLAT_ERR_HIP, the old scene resident and
+ *             unchanged; a failure after the old scene has gone leaves none, as a failed upload does.
+ * SPLAT_ERR_INVALID with the argument named, before the context is looked at: a NULL n_out, an unknown mode, a misaligned
+ * d_index_map_out, a NULL d_selection with n > 0; then a NULL context.  SPLAT_ERR_NO_SCENE: no resident scene;
+ * SPLAT_ERR_INVALID: n is not the resident scene's.  A refused call writes nothing and changes nothing.
+ * Device buffers of the old scene's size that the caller holds (its selections, an index list) do not shrink with it.  The
+ * multi-GPU layer has no counterpart: call it on every rank's context (splat_multi_ctx) with the same mask. */
+int splat_remove_gaussians_device(splat_ctx* ctx, uint64_t n, const void* d_selection, uint32_t mode, void* d_index_map_out,
+                                  uint64_t* n_out, void* producer_stream);
 
 /* The resident values GIVEN BACK, and changed WHERE THEY LIE: with these two an editor that moves, rotates or scales a
  * selection keeps no copy of the scene (after an upload from PLY rows it never had one), and select -> indices -> transform,

@@ -137,6 +137,13 @@ uint64_t select_neighbours(splat_ctx* ctx, float radius, const void* d_source, u
 // all.  Throws what the C call refuses.
 void pick(splat_ctx* ctx, const splat_pick_query& q, const splat_camera& cam, uint32_t n_pixels, const int32_t* pixels_xy,
           const void* d_mask, void* d_results, void* d_layers = nullptr, void* producer_stream = nullptr);
+// Gaussians taken out of the resident scene (splat_remove_gaussians_device): d_selection = n bytes like a selection, mode =
+// SPLAT_REMOVE_SELECTED (the selected go) or SPLAT_REMOVE_UNSELECTED (they stay); the survivors keep their relative original
+// order and are renumbered by rank.  d_index_map_out (n u32, null = not wanted): the new index of every old Gaussian, or
+// 0xFFFFFFFF.  Nothing is sorted; the frames are those of a fresh upload of the survivors.  Returns how many are left.  Throws
+// what the C call refuses.
+uint64_t remove_gaussians_device(splat_ctx* ctx, uint64_t n, const void* d_selection, uint32_t mode = SPLAT_REMOVE_SELECTED,
+                                 void* d_index_map_out = nullptr, void* producer_stream = nullptr);
 
 struct GaussianList {           // src/gaussians.rs:408-416, SoA
     std::vector<float> positions;   // 4 x N (x,y,z,1)

@@ -117,6 +117,10 @@ pub struct SplatPickLayer {
     pub depth: f32, pub alpha: f32, pub coverage: f32,
 }
 
+// splat_remove_gaussians_device's mode: which side of the selection goes
+pub const SPLAT_REMOVE_SELECTED: u32 = 0;
+pub const SPLAT_REMOVE_UNSELECTED: u32 = 1;
+
 // a selection query: a Gaussian passes when every test named in `tests` (SPLAT_SEL_* bits) passes; 0 = all pass
 #[repr(C)] #[derive(Clone, Copy, Default)]
 pub struct SplatSelectQuery {
@@ -195,6 +199,11 @@ extern "C" {
     pub fn splat_pick_device(ctx: *mut SplatCtx, q: *const SplatPickQuery, cam: *const SplatCamera, n_pixels: u32,
                              pixels_xy: *const i32, d_mask: *const c_void, d_results: *mut c_void, d_layers: *mut c_void,
                              producer_stream: *mut c_void) -> c_int;
+    // ... and Gaussians taken out of the scene by a selection (added under ABI 7, found by symbol): mode = SPLAT_REMOVE_*;
+    // d_selection = n bytes like a selection, n the resident scene's; *n_out (required) = the survivors, renumbered by their rank
+    // in original index order; d_index_map_out (n u32, may be null): the new index of every old Gaussian, or 0xFFFF_FFFF
+    pub fn splat_remove_gaussians_device(ctx: *mut SplatCtx, n: u64, d_selection: *const c_void, mode: u32,
+                                         d_index_map_out: *mut c_void, n_out: *mut u64, producer_stream: *mut c_void) -> c_int;
     // the resident values given back, and mapped where they lie (added under ABI 7, found by symbol like those above): the reads
     // are the updates' inverses (same layouts and SPLAT_FIELD_* bits; pos4 gets w = 1; a buffer whose field is not named may be
     // null and is left untouched) and read the scene as a selection does; m = 3x4 row-major affine map in HOST memory, applied

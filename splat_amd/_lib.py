@@ -48,6 +48,9 @@ FIELD_POS, FIELD_COV3D, FIELD_OPACITY, FIELD_SH = 1, 2, 4, 8
 SEL_VOLUME, SEL_SCREEN, SEL_DEPTH, SEL_OPACITY = 1, 2, 4, 8
 SEL_OP_SET, SEL_OP_ADD, SEL_OP_SUBTRACT, SEL_OP_INTERSECT = 0, 1, 2, 3
 
+# SPLAT_REMOVE_*: which side of a selection splat_remove_gaussians_device takes out, and what its index map says of those
+REMOVE_SELECTED, REMOVE_UNSELECTED, REMOVED_INDEX = 0, 1, 0xFFFFFFFF
+
 
 class SelectQuery(C.Structure):
     """splat_select_query: a Gaussian passes when every test named in `tests` passes (0: all pass)"""
@@ -118,6 +121,8 @@ SYMBOLS = [
                                                  C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]),
     ("splat_pick_device", C.c_int, [C.c_void_p, C.POINTER(PickQuery), C.POINTER(CameraC), C.c_uint32, C.POINTER(C.c_int32), C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("splat_remove_gaussians_device", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64),
+                                                C.c_void_p]),
     ("splat_read_scene_device", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("splat_read_gaussians_device", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p]),

@@ -462,6 +462,15 @@ void pick(splat_ctx* ctx, const splat_pick_query& q, const splat_camera& cam, ui
     check(splat_pick_device(ctx, &q, &cam, n_pixels, pixels_xy, d_mask, d_results, d_layers, producer_stream), ctx, "splat_pick_device");
 }
 
+uint64_t remove_gaussians_device(splat_ctx* ctx, uint64_t n, const void* d_selection, uint32_t mode, void* d_index_map_out,
+                                 void* producer_stream) {
+    if (!ctx) throw std::runtime_error("remove_gaussians_device: no context");
+    uint64_t n_after = 0;
+    check(splat_remove_gaussians_device(ctx, n, d_selection, mode, d_index_map_out, &n_after, producer_stream), ctx,
+          "splat_remove_gaussians_device");
+    return n_after;
+}
+
 // load_from_ply (src/gaussians.rs:375-405): the AoS `Vec<Gaussian>` the reference returns, from the same decode
 std::vector<Gaussian> load_from_ply(const std::string& filename) {
     GaussianList l = load_from_ply_soa(filename, 0);

@@ -1,5 +1,5 @@
 // splat_internal.h -- shared between the host files (splat_api.hip, splat_scene.hip) and the kernel files (splat_kernels.hip,
-// splat_ply.hip, splat_ply_encode.hip, splat_update.hip, splat_select.hip, splat_neighbours.hip, splat_pick.hip).
+// splat_ply.hip, splat_ply_encode.hip, splat_update.hip, splat_select.hip, splat_compact.hip, splat_neighbours.hip, splat_pick.hip).
 #ifndef SPLAT_INTERNAL_H
 #define SPLAT_INTERNAL_H
 #include <hip/hip_runtime.h>
@@ -242,6 +242,17 @@ constexpr unsigned int SELECT_SCAN_ROUND = 256; // workgroup counts the scan tak
 inline uint64_t selection_groups(const void* mask, uint64_t n) { return (((uintptr_t)mask & 15u) + n + SELECT_SPAN - 1) / SELECT_SPAN; }
 void launch_selection_indices(hipStream_t s, uint64_t n, const unsigned char* mask, unsigned int* out, uint64_t capacity,
                               unsigned int* counts);
+// (splat_select.hip's scan on its own: counts[0..g) -> their exclusive prefix sums, counts[g] = the total)
+void launch_count_scan(hipStream_t s, unsigned int g, unsigned int* counts);
+// ... and Gaussians taken out of the scene by one (splat_compact.hip).  launch_index_map: behind launch_selection_indices
+// (with no room for indices: the counts and their scan alone) on the same mask, `offsets` the counts it scanned; map[i] (n
+// words) = the rank of Gaussian i among the survivors, or REMOVED_INDEX.  launch_compact_scene: the survivors' planes and
+// new indices from the scene of n slots to one of n2, slot order kept; block_counts: (n + 255) / 256 + 1 words of scratch.
+constexpr unsigned int REMOVED_INDEX = 0xFFFFFFFFu;
+void launch_index_map(hipStream_t s, uint64_t n, const unsigned char* mask, const unsigned int* offsets, uint32_t mode,
+                      unsigned int* map);
+void launch_compact_scene(hipStream_t s, uint64_t n, uint64_t n2, const float4* planes, const unsigned int* orig,
+                          const unsigned int* map, unsigned int* block_counts, float4* planes2, unsigned int* orig2);
 // ... and a selection by neighbourhood (splat_neighbours.hip; r2: the radius squared, finite).  *pairs (zeroed by the caller) +=
 // the ordered pairs of K1 blocks whose bounds are within reach of each other.  counts[i] (n words, ORIGINAL index order) =
 // min(cap, the Gaussians j != i with source[j] != 0 -- source == nullptr: all -- whose centre is within reach of i's).

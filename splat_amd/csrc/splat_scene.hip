@@ -1,7 +1,8 @@
 // splat_scene.hip -- everything that puts values into the resident scene: the uploads (host buffers, device buffers, PLY
 // rows), the in-place edits, K0 (cov3d) and the scene's layout read back -- and the selections read from it, which name the
-// Gaussians such an edit is for.  Host side only, no device code: the kernels are splat_kernels.hip's (order, bounds,
-// packing), splat_ply.hip's, splat_ply_encode.hip's, splat_update.hip's, splat_transform.hip's, splat_select.hip's, splat_neighbours.hip's and splat_pick.hip's.
+// Gaussians such an edit is for, and the removal that takes them out.  Host side only, no device code: the kernels are
+// splat_kernels.hip's (order, bounds, packing), splat_ply.hip's, splat_ply_encode.hip's, splat_update.hip's,
+// splat_transform.hip's, splat_select.hip's, splat_compact.hip's, splat_neighbours.hip's and splat_pick.hip's.
 // What the frame scheduler (splat_api.hip) holds per scene is behind the seam of splat_context.h.
 #include <algorithm>
 #include <cmath>
@@ -38,6 +39,13 @@ struct Temps {
     void release(T*& p) {                      // ahead of the owner: what comes next needs the room
         bufs.erase(std::remove(bufs.begin(), bufs.end(), (void*)p), bufs.end());
         dfree(p);
+    }
+    template <typename T>
+    T* keep(T*& p) {                           // handed on: the buffer outlives the call (a removal's new scene arrays)
+        bufs.erase(std::remove(bufs.begin(), bufs.end(), (void*)p), bufs.end());
+        T* q = p;
+        p = nullptr;
+        return q;
     }
     hipError_t event(hipEvent_t* e) {          // (with timing)
         hipError_t err = hipEventCreate(e);
@@ -124,10 +132,9 @@ void block_bounds(uint64_t n, const float* pos4, const float* cov3d, const std::
     }
 }
 
-// the buffers that live as long as the scene (the bounds apart: the host path makes them once it has their values)
-hipError_t alloc_scene(splat_ctx* c, uint64_t n) {
-    HIP_RET(dmalloc(c, &c->planes, sizeof(float4) * SCENE_PLANES * n));
-    HIP_RET(dmalloc(c, &c->orig, sizeof(unsigned int) * n));
+// The buffers that live as long as the scene, in two parts: the frame slots' per-Gaussian buffers (a removal makes them for
+// the scene it has compacted) ...
+hipError_t alloc_slot_buffers(splat_ctx* c, uint64_t n) {
     for (Slot& s : c->slots) {
         HIP_RET(dmalloc(c, &s.recs, sizeof(Rec) * n));
         HIP_RET(dmalloc(c, &s.blockinfo, sizeof(unsigned int) * ((n + 255) / 256)));
@@ -139,6 +146,12 @@ hipError_t alloc_scene(splat_ctx* c, uint64_t n) {
         }
     }
     return hipSuccess;
+}
+// ... and, in front of them, the scene arrays (the bounds apart: the host path makes them once it has their values)
+hipError_t alloc_scene(splat_ctx* c, uint64_t n) {
+    HIP_RET(dmalloc(c, &c->planes, sizeof(float4) * SCENE_PLANES * n));
+    HIP_RET(dmalloc(c, &c->orig, sizeof(unsigned int) * n));
+    return alloc_slot_buffers(c, n);
 }
 // Work the caller enqueued on `producer` comes first: the context's stream waits for an event recorded there.
 hipError_t follow_producer(splat_ctx* c, void* producer) {
@@ -246,6 +259,15 @@ const char* pick_refusal(const splat_pick_query* q, const splat_camera* cam, uin
     for (uint32_t p = 0; p < n_pixels; ++p)
         if (pixels_xy[2 * p] < 0 || pixels_xy[2 * p] >= W || pixels_xy[2 * p + 1] < 0 || pixels_xy[2 * p + 1] >= H)
             return "pixels_xy: a pixel lies outside [0, w) x [0, h)";
+    return nullptr;
+}
+
+// what splat_remove_gaussians_device refuses before it looks at the context or touches HIP; nullptr: nothing
+const char* remove_refusal(uint64_t n, const void* selection, uint32_t mode, const void* index_map, const uint64_t* n_out) {
+    if (!n_out) return "NULL n_out";
+    if (mode > SPLAT_REMOVE_UNSELECTED) return "unknown mode";
+    if ((uintptr_t)index_map & 3u) return "d_index_map_out is misaligned (4 bytes)";
+    if (n && !selection) return "NULL d_selection";
     return nullptr;
 }
 
@@ -415,7 +437,7 @@ int splat_update_scene_device(splat_ctx* c, uint64_t n, uint32_t fields, const v
     if (!c) return fail(c, SPLAT_ERR_INVALID, "NULL context");
     if (const char* why = update_refusal(n, fields, d_pos4, d_cov3d, d_opacity, d_sh)) return fail(c, SPLAT_ERR_INVALID, why);
     if (c->n == 0) return fail(c, SPLAT_ERR_NO_SCENE, "no resident scene to update");
-    if (n != c->n) return fail(c, SPLAT_ERR_INVALID, "n is not the resident scene's (changing n is an upload)");
+    if (n != c->n) return fail(c, SPLAT_ERR_INVALID, "n is not the resident scene's (changing n is an upload or a removal)");
     if (fields == 0) return SPLAT_OK;
     int rc = end_frames_for_edit(c);
     if (rc != SPLAT_OK) return rc;
@@ -734,6 +756,75 @@ int splat_pick_device(splat_ctx* c, const splat_pick_query* q, const splat_camer
     launch_pick(c->stream, c->n, c->planes, c->orig, (const unsigned char*)d_mask, v, *q, n_pixels, d_pixels, bound, pt, d_results, d_layers);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SPLAT_OK;
+}
+
+// Gaussians taken out of the scene by a selection.  The mask is counted as a READ of the scene -- a call that finds nothing
+// to remove has been one -- and only then does the call become an edit that changes n: the new scene arrays are made and
+// filled while the old scene is whole, the old one and the frame slots' per-Gaussian buffers go after the compaction has
+// completed, and from there on a failure leaves no scene, as in an upload.  The order is the old one's without the slots
+// that went: nothing is sorted.
+int splat_remove_gaussians_device(splat_ctx* c, uint64_t n, const void* d_selection, uint32_t mode, void* d_index_map_out,
+                                  uint64_t* n_out, void* producer_stream) {
+    // (the arguments are judged before the context is looked at, as the selections do it)
+    if (const char* why = remove_refusal(n, d_selection, mode, d_index_map_out, n_out)) return fail(c, SPLAT_ERR_INVALID, why);
+    if (!c) return fail(c, SPLAT_ERR_INVALID, "NULL context");
+    if (c->n == 0) return fail(c, SPLAT_ERR_NO_SCENE, "no resident scene to remove from");
+    if (n != c->n) return fail(c, SPLAT_ERR_INVALID, "n is not the resident scene's");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    int rc = ctx_quiesce(c);
+    if (rc != SPLAT_OK) return rc;
+    const unsigned char* mask = (const unsigned char*)d_selection;
+    unsigned int* d_map = (unsigned int*)d_index_map_out;
+    uint64_t n2 = 0;
+    SceneGuard guard{c, true, false};          // armed once the old scene has gone
+    {
+        Temps t(c);
+        unsigned int *d_counts = nullptr, *d_blocks = nullptr;
+        unsigned int total = 0;
+        const uint64_t g = selection_groups(mask, n);
+        HIP_TRY(c, t.alloc(&d_counts, sizeof(unsigned int) * (g + 1)));
+        HIP_TRY(c, follow_producer(c, producer_stream));
+        launch_selection_indices(c->stream, n, mask, nullptr, 0, d_counts);      // (no room for indices: the counts and their scan)
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(&total, d_counts + g, sizeof total, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        n2 = mode == SPLAT_REMOVE_UNSELECTED ? (uint64_t)total : n - total;
+        if (n2 != n) {
+            rc = end_frames_for_edit(c);
+            if (rc != SPLAT_OK) return rc;
+        }
+        if (n2 == n || n2 == 0) {              // nothing to compact: the map alone, the identity or REMOVED_INDEX throughout
+            if (d_map) {
+                launch_index_map(c->stream, n, mask, d_counts, mode, d_map);
+                HIP_TRY(c, hipGetLastError());
+                HIP_TRY(c, hipStreamSynchronize(c->stream));
+            }
+            if (n2 == 0) free_scene(c);
+            *n_out = n2;
+            return SPLAT_OK;
+        }
+        float4* planes2 = nullptr; unsigned int* orig2 = nullptr; BlockBounds* bounds2 = nullptr;
+        HIP_TRY(c, t.alloc(&planes2, sizeof(float4) * SCENE_PLANES * n2));
+        HIP_TRY(c, t.alloc(&orig2, sizeof(unsigned int) * n2));
+        HIP_TRY(c, t.alloc(&bounds2, sizeof(BlockBounds) * ((n2 + 255) / 256)));
+        HIP_TRY(c, t.alloc(&d_blocks, sizeof(unsigned int) * ((n + 255) / 256 + 1)));
+        if (!d_map) HIP_TRY(c, t.alloc(&d_map, sizeof(unsigned int) * n));
+        launch_index_map(c->stream, n, mask, d_counts, mode, d_map);
+        launch_compact_scene(c->stream, n, n2, c->planes, c->orig, d_map, d_blocks, planes2, orig2);
+        launch_plane_bounds(c->stream, n2, planes2, nullptr, bounds2);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        // the old scene goes, with the inverse and the host copy of its order; the new arrays take its place
+        free_scene(c);
+        guard.armed = true;
+        c->planes = t.keep(planes2); c->orig = t.keep(orig2); c->bounds = t.keep(bounds2);
+        HIP_TRY(c, alloc_slot_buffers(c, n2));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    scene_installed(c, n2);
+    guard.armed = false;
+    *n_out = n2;
     return SPLAT_OK;
 }
 

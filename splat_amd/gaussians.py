@@ -45,7 +45,8 @@ class GaussianList:
 class DeviceGaussians:
     """Device addresses (ints) of a GaussianList's buffers on one renderer's GPU: positions, scales, opacities, rotations,
     sh, cov3d; n Gaussians.  Allocations of that renderer's context (they count in its device_bytes()), owned by this object:
-    free() them before the renderer is closed.  Any context on the same GPU may read them."""
+    free() them before the renderer is closed.  Any context on the same GPU may read them.  They are a copy the renderer
+    does not follow: after Renderer.remove they still hold the old n rows in the old numbering -- stale for refresh()."""
     FIELDS = ("positions", "scales", "opacities", "rotations", "sh", "cov3d")
 
     def __init__(self, renderer, g):

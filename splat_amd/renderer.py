@@ -367,6 +367,35 @@ class Renderer:
                                                            C.c_void_p(st)))
         return int(count.value)
 
+    def remove(self, selection, keep=False, index_map=None, stream=None, n=None):
+        """splat_remove_gaussians_device: the selected Gaussians taken out of the resident scene (keep=True: everything BUT
+        them -- a crop), the survivors compacted on the GPU.  `selection` is select's: n bytes of device memory, original index
+        order, nonzero = selected (a torch.uint8 / torch.bool tensor, or a device address; n= names another length than the
+        resident scene's, which the library then refuses).  Survivors keep their relative original order and are renumbered
+        by rank: from here on every index, row and selection byte means the new numbering, and self.n is the new count.
+        index_map: a device buffer of n 32-bit elements that receives, per old Gaussian, its new index or 0xFFFFFFFF
+        (_lib.REMOVED_INDEX) -- what carries the caller's own per-Gaussian arrays and other selections across the call; a
+        DeviceGaussians (GaussianList.to_device) made before the call still holds the old rows and is stale.  Nothing is
+        sorted, freed memory is given back, and the frames that follow are those of upload() of the survivors, byte for byte.
+        A selection that removes nothing leaves everything kept from frame to frame in place; one that removes everything
+        leaves no scene.  Synchronous; frames in flight end first and show the scene as it was.  Returns the new n."""
+        dev = int(self.config.device)
+        n = self.n if n is None else int(n)
+        ps = _byte_mask_address(selection, "selection", n, dev)
+        pm = 0
+        if index_map is not None:
+            if not isinstance(index_map, int) and hasattr(index_map, "element_size") and int(index_map.element_size()) != 4:
+                raise TypeError("index_map: 32-bit indices expected, got %s" % getattr(index_map, "dtype", None))
+            pm = _device_address(index_map, "index_map", None, dev, any_dtype=True)
+            if not isinstance(index_map, int) and hasattr(index_map, "numel") and int(index_map.numel()) != n:
+                raise ValueError("index_map: %d elements expected, got %d" % (n, int(index_map.numel())))
+        st = _producer_stream(stream, (selection, index_map))
+        n_after = C.c_uint64()
+        self._check(self._L.splat_remove_gaussians_device(self._h, n, C.c_void_p(ps), _lib.REMOVE_UNSELECTED if keep else _lib.REMOVE_SELECTED,
+                                                          C.c_void_p(pm), C.byref(n_after), C.c_void_p(st)))
+        self.n = int(n_after.value)
+        return self.n
+
     block_pairs = None          # what the most recent select_neighbours was bounded by (see there)
 
     def select_neighbours(self, selection, radius, *, source=None, at_least=0, at_most=None, op="set", counts=None,
