@@ -46,7 +46,8 @@ extern "C" {
  * splat_sh_rotation_blocks, splat_rotate_sh_scene_device and splat_rotate_sh_gaussians_device, and
  * splat_select_neighbours_device, and splat_encode_ply_scene_device and splat_encode_ply_gaussians_device, and
  * splat_pick_device (and the splat_pick_query, splat_pick_result, splat_pick_layer and SPLAT_PICK_* values it takes), and
- * splat_remove_gaussians_device (and the SPLAT_REMOVE_* values it takes). */
+ * splat_remove_gaussians_device (and the SPLAT_REMOVE_* values it takes), and
+ * splat_append_gaussians_device and splat_reorder_scene_device. */
 
 /* modes: bit flags, 0 = the default */
 #define SPLAT_MODE_EXACT 0       /* back-to-front, 8-bit truncation per splat as blend() does it; the exponential of
@@ -440,6 +441,58 @@ int splat_pick_device(splat_ctx* ctx, const splat_pick_query* q, const splat_cam
  * multi-GPU layer has no counterpart: call it on every rank's context (splat_multi_ctx) with the same mask. */
 int splat_remove_gaussians_device(splat_ctx* ctx, uint64_t n, const void* d_selection, uint32_t mode, void* d_index_map_out,
                                   uint64_t* n_out, void* producer_stream);
+
+/* Gaussians ADDED to the resident scene -- a paste, a duplicate, a second PLY merged into the open one -- without the scene
+ * being read back, concatenated and uploaded again: the resident values are copied where they lie (256 B read and written
+ * per resident Gaussian, nothing of them sorted), only the new rows are ordered and packed.
+ * The four buffers are splat_upload_scene_device's: device memory, [m,4], [m,9], [m], [m,48] float32, and producer_stream as
+ * there.  n must be the resident scene's; *n_out (required) = n + m.  The new Gaussians get the original indices
+ * n .. n+m-1 in row order and every resident Gaussian keeps its index: no index map is needed.  Synchronous.
+ *   m == 0   SPLAT_OK, *n_out = n, and the call has READ nothing: region layouts, hints, retained lists and the inverse
+ *            order all survive, splat_device_bytes() has not moved.
+ *   else     an edit that also changes n, as a removal is: frames queued before it show the scene as it was (one found
+ *            skipped stays pending for splat_sync), afterwards the state kept from frame to frame starts over and the inverse
+ *            order is made again on first use.  The scene's order (splat_get_scene_layout): slots 0 .. n-1 are untouched,
+ *            slots n .. n+m-1 hold the new rows in the Morton order of the appended positions ALONE (their own finite box,
+ *            ties in row order) -- not a new sort of everything.  The bounds of the blocks wholly below slot n keep their
+ *            bits, the others are those of the values now in them.  The appended rows are stored with the bits an upload
+ *            gives them, and the frames that follow are those of a fresh splat_upload_scene of the concatenated arrays, byte
+ *            for byte, in every mode (depth ties go by original index, not by slot).  splat_device_bytes() is what it is
+ *            after uploading the n + m Gaussians over the old scene; during the call the old scene and the new planes
+ *            (256 B per Gaussian of n + m, and 16 B per new row for its sort) exist side by side.  If those cannot be
+ *            allocated: SPLAT_ERR_HIP, the old scene resident and unchanged; a failure after the old scene has gone leaves
+ *            none, as a failed upload does.
+ * SPLAT_ERR_INVALID with the argument named, before the context is looked at: a NULL n_out, n + m >= 0xFFFFFFFF, with m > 0
+ * a NULL field pointer; then a NULL context.  SPLAT_ERR_NO_SCENE: no resident scene (this call does not upload: an empty
+ * context takes splat_upload_scene_device); SPLAT_ERR_INVALID: n is not the resident scene's.  A refused call writes
+ * nothing, not even *n_out, and changes nothing.
+ * Device buffers of the old scene's size that the caller holds (its selections, a read-back) do not grow with it: a
+ * selection wants n + m bytes from here on.  The multi-GPU layer has no counterpart: call it on every rank's context
+ * (splat_multi_ctx) with the same rows. */
+int splat_append_gaussians_device(splat_ctx* ctx, uint64_t n, uint64_t m, const void* d_pos4, const void* d_cov3d,
+                                  const void* d_opacity, const void* d_sh, uint64_t* n_out, void* producer_stream);
+
+/* The resident scene PUT BACK IN ORDER: its slots as a fresh upload of its CURRENT values would order them.  The order of a
+ * scene is the Morton order of its upload; splat_transform_gaussians_device and splat_update_gaussians_device move Gaussians
+ * without moving their slots, a removal can shrink the box, an append orders only what it adds.  A stale order costs time
+ * only -- frames do not depend on it -- but it costs: K1 culls by per-block bounds and splat_select_neighbours_device is
+ * refused by the count of block pairs within reach, and a block with one member far away makes both worse.
+ * The resident positions are read in original index order, sorted as an upload sorts them, and compared with the order
+ * in place.  *moved_out (nullable) = the slots that hold another Gaussian in the new order than they do now.
+ *   0        the call has READ the scene as a selection does: nothing is installed, everything kept from frame to frame
+ *            survives, splat_device_bytes() is where it was.
+ *   else     an edit, as a removal is, with n unchanged: the planes are gathered into the new order, every block's bounds
+ *            are made again, the state kept from frame to frame starts over and the inverse order is made again on first
+ *            use.  Afterwards splat_get_scene_layout gives the order and, bit for bit, the bounds of a fresh
+ *            splat_upload_scene of the resident values; values and original indices are unchanged; the frames before and
+ *            after are byte-identical to each other and to the fresh upload's, and so are records, tile lists and counts.
+ *            During the call the old and the new planes exist side by side (256 B per Gaussian; 32 B per Gaussian of
+ *            temporaries while the order is made, gone before the new planes are); splat_device_bytes() afterwards is what
+ *            it is after uploading the same n over the old scene.  Allocation failures as for the append.
+ * SPLAT_ERR_INVALID: a NULL context; SPLAT_ERR_NO_SCENE: no resident scene.  Synchronous.  An append followed by a reorder
+ * leaves the context as splat_upload_scene_device of the concatenation does, in every observable respect.  The multi-GPU
+ * layer has no counterpart: call it on every rank's context. */
+int splat_reorder_scene_device(splat_ctx* ctx, uint64_t* moved_out);
 
 /* The resident values GIVEN BACK, and changed WHERE THEY LIE: with these two an editor that moves, rotates or scales a
  * selection keeps no copy of the scene (after an upload from PLY rows it never had one), and select -> indices -> transform,

@@ -144,6 +144,16 @@ void pick(splat_ctx* ctx, const splat_pick_query& q, const splat_camera& cam, ui
 // what the C call refuses.
 uint64_t remove_gaussians_device(splat_ctx* ctx, uint64_t n, const void* d_selection, uint32_t mode = SPLAT_REMOVE_SELECTED,
                                  void* d_index_map_out = nullptr, void* producer_stream = nullptr);
+// Gaussians added to the resident scene (splat_append_gaussians_device): m rows in splat_upload_scene_device's four device
+// buffers; they get the original indices n .. n+m-1, the resident ones keep theirs and their slots, the new rows are ordered
+// among themselves behind them.  The frames are those of a fresh upload of the concatenation.  Returns n + m.  Throws what
+// the C call refuses -- a context without a scene among it: that takes an upload.
+uint64_t append_gaussians_device(splat_ctx* ctx, uint64_t n, uint64_t m, const void* d_pos4, const void* d_cov3d,
+                                 const void* d_opacity, const void* d_sh, void* producer_stream = nullptr);
+// The resident scene put into the order a fresh upload of its current values would have (splat_reorder_scene_device): worth
+// calling after appends, indexed transforms or updates of positions, and removals.  Returns how many slots hold another
+// Gaussian than before; 0: the call has been a read.
+uint64_t reorder_scene_device(splat_ctx* ctx);
 
 struct GaussianList {           // src/gaussians.rs:408-416, SoA
     std::vector<float> positions;   // 4 x N (x,y,z,1)

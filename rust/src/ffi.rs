@@ -204,6 +204,15 @@ extern "C" {
     // in original index order; d_index_map_out (n u32, may be null): the new index of every old Gaussian, or 0xFFFF_FFFF
     pub fn splat_remove_gaussians_device(ctx: *mut SplatCtx, n: u64, d_selection: *const c_void, mode: u32,
                                          d_index_map_out: *mut c_void, n_out: *mut u64, producer_stream: *mut c_void) -> c_int;
+    // ... and Gaussians added to it (added under ABI 7, found by symbol): m rows in splat_upload_scene_device's four device
+    // buffers, n the resident scene's; *n_out (required) = n + m; the new rows get the original indices n .. n+m-1 and are
+    // ordered among themselves behind the resident slots, which stay.  No scene: SPLAT_ERR_NO_SCENE (that takes an upload)
+    pub fn splat_append_gaussians_device(ctx: *mut SplatCtx, n: u64, m: u64, d_pos4: *const c_void, d_cov3d: *const c_void,
+                                         d_opacity: *const c_void, d_sh: *const c_void, n_out: *mut u64,
+                                         producer_stream: *mut c_void) -> c_int;
+    // ... and its slots put into the order a fresh upload of its current values would have; *moved_out (may be null) = the
+    // slots that hold another Gaussian than before, 0: the call has been a read
+    pub fn splat_reorder_scene_device(ctx: *mut SplatCtx, moved_out: *mut u64) -> c_int;
     // the resident values given back, and mapped where they lie (added under ABI 7, found by symbol like those above): the reads
     // are the updates' inverses (same layouts and SPLAT_FIELD_* bits; pos4 gets w = 1; a buffer whose field is not named may be
     // null and is left untouched) and read the scene as a selection does; m = 3x4 row-major affine map in HOST memory, applied

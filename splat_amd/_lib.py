@@ -123,6 +123,9 @@ SYMBOLS = [
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     ("splat_remove_gaussians_device", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64),
                                                 C.c_void_p]),
+    ("splat_append_gaussians_device", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.POINTER(C.c_uint64), C.c_void_p]),
+    ("splat_reorder_scene_device", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     ("splat_read_scene_device", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("splat_read_gaussians_device", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p]),

@@ -471,6 +471,22 @@ uint64_t remove_gaussians_device(splat_ctx* ctx, uint64_t n, const void* d_selec
     return n_after;
 }
 
+uint64_t append_gaussians_device(splat_ctx* ctx, uint64_t n, uint64_t m, const void* d_pos4, const void* d_cov3d,
+                                 const void* d_opacity, const void* d_sh, void* producer_stream) {
+    if (!ctx) throw std::runtime_error("append_gaussians_device: no context");
+    uint64_t n_after = 0;
+    check(splat_append_gaussians_device(ctx, n, m, d_pos4, d_cov3d, d_opacity, d_sh, &n_after, producer_stream), ctx,
+          "splat_append_gaussians_device");
+    return n_after;
+}
+
+uint64_t reorder_scene_device(splat_ctx* ctx) {
+    if (!ctx) throw std::runtime_error("reorder_scene_device: no context");
+    uint64_t moved = 0;
+    check(splat_reorder_scene_device(ctx, &moved), ctx, "splat_reorder_scene_device");
+    return moved;
+}
+
 // load_from_ply (src/gaussians.rs:375-405): the AoS `Vec<Gaussian>` the reference returns, from the same decode
 std::vector<Gaussian> load_from_ply(const std::string& filename) {
     GaussianList l = load_from_ply_soa(filename, 0);

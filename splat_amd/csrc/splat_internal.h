@@ -253,6 +253,18 @@ void launch_index_map(hipStream_t s, uint64_t n, const unsigned char* mask, cons
                       unsigned int* map);
 void launch_compact_scene(hipStream_t s, uint64_t n, uint64_t n2, const float4* planes, const unsigned int* orig,
                           const unsigned int* map, unsigned int* block_counts, float4* planes2, unsigned int* orig2);
+// ... and Gaussians added to it, and its slots put back in order (splat_append.hip).  launch_grow_scene: the n resident slots'
+// planes and indices from stride n to stride n2.  launch_pack_append: behind launch_scene_order of the m new rows into
+// orig2 + n; row orig2[n + j] packed into slot n + j of the arrays of n + m slots, orig2[n + j] += n.  launch_order_moved:
+// *moved (zeroed by the caller) += the slots j with orig[j] != orig2[j].  launch_permute_scene: slot j of planes2 from slot
+// inv[orig2[j]] of planes (inv: launch_inverse_order of the order planes lie in), both of n slots.
+void launch_grow_scene(hipStream_t s, uint64_t n, uint64_t n2, const float4* planes, const unsigned int* orig, float4* planes2,
+                       unsigned int* orig2);
+void launch_pack_append(hipStream_t s, uint64_t n, uint64_t m, const float* pos4, const float* cov3d, const float* opacity,
+                        const float* sh, float4* planes2, unsigned int* orig2);
+void launch_order_moved(hipStream_t s, uint64_t n, const unsigned int* orig, const unsigned int* orig2, unsigned long long* moved);
+void launch_permute_scene(hipStream_t s, uint64_t n, const float4* planes, const unsigned int* inv, const unsigned int* orig2,
+                          float4* planes2);
 // ... and a selection by neighbourhood (splat_neighbours.hip; r2: the radius squared, finite).  *pairs (zeroed by the caller) +=
 // the ordered pairs of K1 blocks whose bounds are within reach of each other.  counts[i] (n words, ORIGINAL index order) =
 // min(cap, the Gaussians j != i with source[j] != 0 -- source == nullptr: all -- whose centre is within reach of i's).

@@ -1,8 +1,9 @@
 // splat_scene.hip -- everything that puts values into the resident scene: the uploads (host buffers, device buffers, PLY
 // rows), the in-place edits, K0 (cov3d) and the scene's layout read back -- and the selections read from it, which name the
-// Gaussians such an edit is for, and the removal that takes them out.  Host side only, no device code: the kernels are
-// splat_kernels.hip's (order, bounds, packing), splat_ply.hip's, splat_ply_encode.hip's, splat_update.hip's,
-// splat_transform.hip's, splat_select.hip's, splat_compact.hip's, splat_neighbours.hip's and splat_pick.hip's.
+// Gaussians such an edit is for, the removal that takes them out, the append that adds some and the reorder.  Host side only,
+// no device code: the kernels are splat_kernels.hip's (order, bounds, packing), splat_ply.hip's, splat_ply_encode.hip's,
+// splat_update.hip's, splat_transform.hip's, splat_select.hip's, splat_compact.hip's, splat_append.hip's,
+// splat_neighbours.hip's and splat_pick.hip's.
 // What the frame scheduler (splat_api.hip) holds per scene is behind the seam of splat_context.h.
 #include <algorithm>
 #include <cmath>
@@ -268,6 +269,18 @@ const char* remove_refusal(uint64_t n, const void* selection, uint32_t mode, con
     if (mode > SPLAT_REMOVE_UNSELECTED) return "unknown mode";
     if ((uintptr_t)index_map & 3u) return "d_index_map_out is misaligned (4 bytes)";
     if (n && !selection) return "NULL d_selection";
+    return nullptr;
+}
+
+// what splat_append_gaussians_device refuses before it looks at the context or touches HIP; nullptr: nothing
+const char* append_refusal(uint64_t n, uint64_t m, const void* pos4, const void* cov3d, const void* opacity, const void* sh,
+                           const uint64_t* n_out) {
+    if (!n_out) return "NULL n_out";
+    if (n >= 0xFFFFFFFFull || m >= 0xFFFFFFFFull - n) return "n + m: too many Gaussians (an index is 32-bit)";
+    if (m && !pos4) return "NULL d_pos4";
+    if (m && !cov3d) return "NULL d_cov3d";
+    if (m && !opacity) return "NULL d_opacity";
+    if (m && !sh) return "NULL d_sh";
     return nullptr;
 }
 
@@ -825,6 +838,119 @@ int splat_remove_gaussians_device(splat_ctx* c, uint64_t n, const void* d_select
     scene_installed(c, n2);
     guard.armed = false;
     *n_out = n2;
+    return SPLAT_OK;
+}
+
+// Gaussians added behind the resident ones: the removal's opposite, and like it an edit that changes n.  The new arrays of
+// n + m slots are made and filled while the old scene is whole -- the resident slots copied, the new rows sorted among
+// themselves and packed behind them -- and then take its place as a removal's do.  Nothing resident is sorted: the blocks
+// wholly below slot n keep their bounds, the others are made again from the new planes.
+int splat_append_gaussians_device(splat_ctx* c, uint64_t n, uint64_t m, const void* d_pos4, const void* d_cov3d, const void* d_opacity,
+                                  const void* d_sh, uint64_t* n_out, void* producer_stream) {
+    // (the arguments are judged before the context is looked at, as the removal does it)
+    if (const char* why = append_refusal(n, m, d_pos4, d_cov3d, d_opacity, d_sh, n_out)) return fail(c, SPLAT_ERR_INVALID, why);
+    if (!c) return fail(c, SPLAT_ERR_INVALID, "NULL context");
+    if (c->n == 0) return fail(c, SPLAT_ERR_NO_SCENE, "no resident scene to append to (an empty context takes an upload)");
+    if (n != c->n) return fail(c, SPLAT_ERR_INVALID, "n is not the resident scene's");
+    if (m == 0) { *n_out = n; return SPLAT_OK; }
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    int rc = ctx_quiesce(c);
+    if (rc != SPLAT_OK) return rc;
+    rc = end_frames_for_edit(c);
+    if (rc != SPLAT_OK) return rc;
+    const uint64_t n2 = n + m, nb2 = (n2 + 255) / 256, whole = n / 256;      // whole: the blocks that lie below slot n altogether
+    const float* pos4 = (const float*)d_pos4;
+    SceneGuard guard{c, true, false};          // armed once the old scene has gone
+    {
+        Temps t(c);
+        float4* planes2 = nullptr; unsigned int* orig2 = nullptr; BlockBounds* bounds2 = nullptr;
+        uint32_t* d_sort = nullptr; unsigned char *d_small = nullptr, *d_dirty = nullptr;
+        HIP_TRY(c, t.alloc(&planes2, sizeof(float4) * SCENE_PLANES * n2));
+        HIP_TRY(c, t.alloc(&orig2, sizeof(unsigned int) * n2));
+        HIP_TRY(c, t.alloc(&bounds2, sizeof(BlockBounds) * nb2));
+        HIP_TRY(c, t.alloc(&d_sort, sizeof(uint32_t) * 4 * m));
+        HIP_TRY(c, t.alloc(&d_small, scene_order_small_bytes(m)));
+        HIP_TRY(c, t.alloc(&d_dirty, nb2));
+        HIP_TRY(c, follow_producer(c, producer_stream));
+        launch_scene_order(c->stream, m, pos4, d_sort, d_small, orig2 + n);
+        launch_grow_scene(c->stream, n, n2, c->planes, c->orig, planes2, orig2);
+        launch_pack_append(c->stream, n, m, pos4, (const float*)d_cov3d, (const float*)d_opacity, (const float*)d_sh, planes2, orig2);
+        if (whole) {
+            HIP_TRY(c, hipMemcpyAsync(bounds2, c->bounds, sizeof(BlockBounds) * whole, hipMemcpyDeviceToDevice, c->stream));
+            HIP_TRY(c, hipMemsetAsync(d_dirty, 0, whole, c->stream));
+        }
+        HIP_TRY(c, hipMemsetAsync(d_dirty + whole, 1, nb2 - whole, c->stream));
+        launch_plane_bounds(c->stream, n2, planes2, d_dirty, bounds2);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        // the old scene goes, with the inverse and the host copy of its order; the new arrays take its place
+        free_scene(c);
+        guard.armed = true;
+        c->planes = t.keep(planes2); c->orig = t.keep(orig2); c->bounds = t.keep(bounds2);
+        HIP_TRY(c, alloc_slot_buffers(c, n2));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    scene_installed(c, n2);
+    guard.armed = false;
+    *n_out = n2;
+    return SPLAT_OK;
+}
+
+// The resident scene put into the order a fresh upload of its current values would have.  The order is made first, as a
+// READ of the scene -- a call that finds every slot where it belongs has been one -- and only then does the call become
+// an edit: the planes are gathered into new arrays while the old scene is whole, and those take its place as a removal's do.
+int splat_reorder_scene_device(splat_ctx* c, uint64_t* moved_out) {
+    if (!c) return fail(c, SPLAT_ERR_INVALID, "NULL context");
+    if (c->n == 0) return fail(c, SPLAT_ERR_NO_SCENE, "no resident scene to reorder");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    int rc = ctx_quiesce(c);
+    if (rc != SPLAT_OK) return rc;
+    const uint64_t n = c->n;
+    unsigned long long moved = 0;
+    SceneGuard guard{c, true, false};          // armed once the old scene has gone
+    {
+        Temps t(c);
+        float* d_pos = nullptr; uint32_t* d_sort = nullptr; unsigned char* d_small = nullptr;
+        unsigned int* orig2 = nullptr; unsigned long long* d_moved = nullptr;
+        HIP_TRY(c, t.alloc(&orig2, sizeof(unsigned int) * n));
+        HIP_TRY(c, t.alloc(&d_pos, sizeof(float) * 4 * n));
+        HIP_TRY(c, t.alloc(&d_sort, sizeof(uint32_t) * 4 * n));
+        HIP_TRY(c, t.alloc(&d_small, scene_order_small_bytes(n)));
+        HIP_TRY(c, t.alloc(&d_moved, sizeof(unsigned long long)));
+        HIP_TRY(c, hipMemsetAsync(d_moved, 0, sizeof(unsigned long long), c->stream));
+        launch_unpack_scene(c->stream, n, SPLAT_FIELD_POS, d_pos, nullptr, nullptr, nullptr, c->orig, c->planes);
+        launch_scene_order(c->stream, n, d_pos, d_sort, d_small, orig2);
+        launch_order_moved(c->stream, n, c->orig, orig2, d_moved);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(&moved, d_moved, sizeof moved, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (moved == 0) {
+            if (moved_out) *moved_out = 0;
+            return SPLAT_OK;
+        }
+        rc = end_frames_for_edit(c);
+        if (rc != SPLAT_OK) return rc;
+        // the sort's arrays have served: they go before the second set of planes is made
+        t.release(d_pos);
+        t.release(d_sort);
+        t.release(d_small);
+        float4* planes2 = nullptr; BlockBounds* bounds2 = nullptr;
+        HIP_TRY(c, t.alloc(&planes2, sizeof(float4) * SCENE_PLANES * n));
+        HIP_TRY(c, t.alloc(&bounds2, sizeof(BlockBounds) * ((n + 255) / 256)));
+        HIP_TRY(c, ensure_inverse(c));
+        launch_permute_scene(c->stream, n, c->planes, c->inv, orig2, planes2);
+        launch_plane_bounds(c->stream, n, planes2, nullptr, bounds2);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        free_scene(c);
+        guard.armed = true;
+        c->planes = t.keep(planes2); c->orig = t.keep(orig2); c->bounds = t.keep(bounds2);
+        HIP_TRY(c, alloc_slot_buffers(c, n));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    scene_installed(c, n);
+    guard.armed = false;
+    if (moved_out) *moved_out = moved;
     return SPLAT_OK;
 }
 

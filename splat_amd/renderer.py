@@ -396,7 +396,79 @@ class Renderer:
         self.n = int(n_after.value)
         return self.n
 
-    block_pairs = None          # what the most recent select_neighbours was bounded by (see there)
+    def append(self, positions, cov3d=None, opacities=None, sh=None, stream=None, m=None):
+        """splat_append_gaussians_device: m Gaussians added to the resident scene from buffers in this GPU's memory (layouts,
+        addresses and stream as in upload_device: positions [m,4], cov3d [m,9], opacities [m], sh [m,48], float32, or a
+        DeviceGaussians; m= with plain addresses).  The new Gaussians get the original indices n .. n+m-1 in row order and
+        every resident one keeps its index, so the caller's index lists stay good; its selections and other buffers of n
+        elements do not grow with the scene.  The resident slots stay where they are and the new rows are ordered among
+        themselves behind them (reorder() puts the whole scene in order); the frames that follow are those of upload() of
+        the concatenated arrays, byte for byte.  With no resident scene (self.n == 0) this is upload_device.  m == 0 changes
+        nothing.  Synchronous; frames in flight end first and show the scene as it was.  Returns the new n."""
+        if hasattr(positions, "positions"):                    # a DeviceGaussians (GaussianList.to_device)
+            d = positions
+            if m is None:
+                m = d.n
+            cov3d = d.cov3d if cov3d is None else cov3d
+            opacities = d.opacities if opacities is None else opacities
+            sh = d.sh if sh is None else sh
+            positions = d.positions
+        for a, what in ((cov3d, "cov3d"), (opacities, "opacities"), (sh, "sh")):
+            if a is None:
+                raise TypeError("%s: an append names all four fields" % what)
+        if m is None and (isinstance(positions, int) or not hasattr(positions, "numel")):
+            raise TypeError("m= is required with plain device addresses")
+        m = _count_of(positions, 4, m)
+        if m < 0:
+            raise ValueError("m: a count is not negative")
+        dev = int(self.config.device)
+        ptrs = [_device_address(a, what, per * m, dev) for a, what, per in
+                ((positions, "positions", 4), (cov3d, "cov3d", 9), (opacities, "opacities", 1), (sh, "sh", 48))]
+        st = _producer_stream(stream, (positions, cov3d, opacities, sh))
+        if self.n == 0:
+            self._check(self._L.splat_upload_scene_device(self._h, m, *[C.c_void_p(p) for p in ptrs], C.c_void_p(st)))
+            self.n = m
+            return self.n
+        n_after = C.c_uint64()
+        self._check(self._L.splat_append_gaussians_device(self._h, self.n, m, *[C.c_void_p(p) for p in ptrs], C.byref(n_after),
+                                                          C.c_void_p(st)))
+        self.n = int(n_after.value)
+        return self.n
+
+    def reorder(self):
+        """splat_reorder_scene_device: the resident scene put into the order upload() of its current values would give it.
+        Appends, indexed transforms and updates of positions, and removals leave the order of the last upload in place, which
+        costs time only -- K1 culls by the bounds of 256 consecutive slots, select_neighbours is bounded by the pairs of
+        such blocks within reach -- and this call takes that cost away: afterwards scene_layout() is a fresh upload's, bounds
+        included, while values, indices and frames are what they were.  Returns how many slots hold another Gaussian than
+        before; 0: nothing was moved and everything kept from frame to frame is still there.  Synchronous."""
+        moved = C.c_uint64()
+        self._check(self._L.splat_reorder_scene_device(self._h, C.byref(moved)))
+        return int(moved.value)
+
+    def duplicate(self, index, k=None, stream=None):
+        """Copies of the Gaussians index[0..k) (as in read_indexed: uint32 / int32 original indices in device memory, in any
+        order, duplicates allowed; k= with a plain address) appended to the resident scene: read_indexed of the four fields
+        into buffers of the library's, then append.  Copy t is Gaussian first_new_index + t.  A copy ties its original in
+        depth at every camera and has the higher index, so it is composited behind it.  What read_indexed refuses is refused
+        here, with nothing appended, and the buffer is freed on every way out.  Returns (first_new_index, n)."""
+        k, pi = self._index_address(index, k)
+        first = self.n
+        if k == 0:
+            return first, self.n
+        st = _producer_stream(stream, (index,))
+        self.read_indexed(pi, stream=st, k=k)              # no field named: the library judges context, scene and k, and nothing else
+        base = self._L.splat_device_alloc(self._h, 4 * 62 * k)
+        if not base:
+            raise SplatError(_lib.ERR_HIP, (self._L.splat_last_error(self._h) or b"duplicate: no device memory for the rows").decode())
+        try:
+            pp, pc, po, ps = base, base + 16 * k, base + 52 * k, base + 56 * k        # [k,4] [k,9] [k] [k,48] float32
+            self.read_indexed(pi, pp, pc, po, ps, stream=st, k=k)
+            return first, self.append(pp, pc, po, ps, m=k)
+        finally:
+            self._L.splat_device_free(self._h, C.c_void_p(base))
+
+    block_pairs = None         # what the most recent select_neighbours was bounded by (see there)
 
     def select_neighbours(self, selection, radius, *, source=None, at_least=0, at_most=None, op="set", counts=None,
                           max_block_pairs=None, stream=None):
