@@ -47,7 +47,9 @@ extern "C" {
  * splat_select_neighbours_device, and splat_encode_ply_scene_device and splat_encode_ply_gaussians_device, and
  * splat_pick_device (and the splat_pick_query, splat_pick_result, splat_pick_layer and SPLAT_PICK_* values it takes), and
  * splat_remove_gaussians_device (and the SPLAT_REMOVE_* values it takes), and
- * splat_append_gaussians_device and splat_reorder_scene_device. */
+ * splat_append_gaussians_device and splat_reorder_scene_device, and
+ * splat_eval_colours_device, splat_select_colour_device (and the splat_colour_query it takes), splat_recolour_scene_device
+ * and splat_recolour_gaussians_device. */
 
 /* modes: bit flags, 0 = the default */
 #define SPLAT_MODE_EXACT 0       /* back-to-front, 8-bit truncation per splat as blend() does it; the exponential of
@@ -574,6 +576,61 @@ int splat_sh_rotation_blocks(const float r[9], float d1[9], float d2[25], float 
 int splat_rotate_sh_scene_device(splat_ctx* ctx, const float r[9]);
 int splat_rotate_sh_gaussians_device(splat_ctx* ctx, uint64_t k, const void* d_index, const float r[9],
                                      void* producer_stream);
+
+/* COLOUR: the colour a Gaussian is drawn with under a camera, a selection by that colour (the "magic wand" that follows a
+ * pick), and a 3x4 map of the colour applied where it is kept -- in the sh coefficients -- without the rows leaving the GPU.
+ * With d = (p - cam_pos) / |p - cam_pos| (|v| = sqrtf((vx vx + vy vy) + vz vz), a division per component), the colour is
+ *   rgb = eval_sh(sh, sh_dim, d) + 0.5
+ * exactly as the vertex stage (K1) computes it for the records of a frame: band 0 always, band 1 with sh_dim > 3, band 2
+ * with > 12, band 3 with > 27; the same f32 operations in the same order, so splat_record.r/g/b bit for bit -- for EVERY
+ * Gaussian, visible or not, and unclamped.  A frame replaces a non-finite colour by +-FLT_MAX before it blends; these calls
+ * do not: a NaN stays a NaN (a Gaussian AT the camera position has a NaN colour from band 1 on).  Of `cam` only cam_pos and
+ * sh_dim are read; a slab set on the context is ignored.
+ * splat_eval_colours_device: three f32 a row into d_rgb_out (device memory, 4-byte aligned).  d_index == NULL: all n
+ * Gaussians in ORIGINAL index order, and k must be n.  Otherwise row t is the colour of Gaussian d_index[t] (u32 original
+ * indices, in any order, duplicates allowed), k <= n rows.
+ * splat_select_colour_device: the colour judged by a query in colour space, with the VOLUME test's semantics of
+ * splat_select_query: with clamp != 0 each channel first becomes v < 0 ? 0 : (v > 1 ? 1 : v) (a NaN stays a NaN), then
+ *   u_k = ((m[4k] r + m[4k+1] g) + m[4k+2] b) + m[4k+3] in f32, unfused, in this order, m = colour_to_unit;
+ *   box: |u_k| <= 1 for k = 0, 1, 2; ellipsoid: (u0 u0 + u1 u1) + u2 u2 <= 1.  A NaN fails.
+ * One map covers a ball around a picked colour (diag(1/tol) | -rgb/tol), per-channel ranges (a box) and a luminance band
+ * (one row of luma weights, two zero rows).  `op`, d_selection and *count_out are splat_select_device's: the library writes
+ * only 0 and 1, SET does not read the selection, ADD and SUBTRACT leave the bytes of Gaussians that do not pass as they are.
+ * Both READ the scene as splat_select_device does: synchronous (producer_stream as for splat_upload_scene_device), ordered on
+ * the context's stream behind the frames in flight; the state kept from frame to frame and splat_device_bytes() are as
+ * before (the indexed form makes the inverse order like the other indexed calls). */
+typedef struct {
+    float    colour_to_unit[12];/* 3x4 row-major affine map, colour -> the unit shape */
+    uint32_t shape;             /* 0 = box, 1 = ellipsoid */
+    uint32_t clamp;             /* nonzero: the colour is clamped to [0, 1] per channel before the map */
+} splat_colour_query;
+/* splat_recolour_*: m = 3x4 row-major in HOST memory, rgb' = A rgb + t with A(i,k) = m[4i+k], t_i = m[4i+3].  The colour is
+ * linear in the coefficients, so for each of the 16 coefficients k, with (r, g, b) = sh[3k .. 3k+3) read before any is
+ * written,
+ *   sh'[3k+i] = (A(i,0) r + A(i,1) g) + A(i,2) b        in f32, unfused, in this order,
+ * and for k == 0 only that + o_i, with o_i = (t_i + 0.5 ((A(i,0) + A(i,1)) + A(i,2)) - 0.5) / C0 evaluated in double from the
+ * f32 entries (C0 = 0.28209479177387814f widened) and rounded to f32 once.  In exact arithmetic eval_sh(sh', d) + 0.5 =
+ * A (eval_sh(sh, d) + 0.5) + t for every direction and every sh_dim, band 0 alone included.  Nothing in sh is checked: with a
+ * non-finite coefficient 0 * inf is NaN, so one inf or NaN makes all three channels of its coefficient NaN.
+ * The two calls are EDITS of sh alone and behave exactly as splat_rotate_sh_*: synchronous, the frames in flight complete
+ * first and show the scene as it was, the state kept from frame to frame starts over; positions and covariances stay, so
+ * the order and the K1 block bounds stay; the frames that follow are those of a fresh splat_upload_scene of the recoloured
+ * arrays, byte for byte.  The indexed form takes distinct indices (a Gaussian named twice may be mapped once or twice;
+ * nothing faults).
+ * The arguments are judged before the context is looked at, and splat_last_error names the argument.  SPLAT_ERR_INVALID: a
+ * NULL q, cam or m; an unknown shape or op; a non-finite entry of m or a non-finite o; a NULL or misaligned d_rgb_out with
+ * k > 0; a NULL d_selection; then a NULL context; SPLAT_ERR_NO_SCENE: no resident scene; SPLAT_ERR_INVALID: k > n, k != n
+ * with a NULL d_index, and -- checked on the device before anything is written or applied -- an index >= n.  k == 0:
+ * SPLAT_OK, nothing done.
+ * The multi-GPU layer (splat_multi_*) has no counterpart, as for the updates: evaluate and select on one rank's context
+ * (every rank holds the whole scene), recolour each rank's (splat_multi_ctx). */
+int splat_eval_colours_device(splat_ctx* ctx, const splat_camera* cam, uint64_t k, const void* d_index, void* d_rgb_out,
+                              void* producer_stream);
+int splat_select_colour_device(splat_ctx* ctx, const splat_colour_query* q, const splat_camera* cam, uint32_t op,
+                               void* d_selection, uint64_t* count_out, void* producer_stream);
+int splat_recolour_scene_device(splat_ctx* ctx, const float m[12]);
+int splat_recolour_gaussians_device(splat_ctx* ctx, uint64_t k, const void* d_index, const float m[12],
+                                    void* producer_stream);
 
 /* Debug / stage parity: the stored scene order and K1 block bounds of the current scene.
  * orig_out: n u32 (slot j holds original Gaussian orig[j]); bounds_out: ceil(n/256) x 8 f32

@@ -119,6 +119,19 @@ void transform_gaussians_device(splat_ctx* ctx, uint64_t k, const void* d_index,
 void sh_rotation_blocks(const float r[9], float d1[9], float d2[25], float d3[49]);
 void rotate_sh_scene_device(splat_ctx* ctx, const float r[9]);
 void rotate_sh_gaussians_device(splat_ctx* ctx, uint64_t k, const void* d_index, const float r[9], void* producer_stream = nullptr);
+// Colour (splat_eval_colours_device, splat_select_colour_device, splat_recolour_scene_device, splat_recolour_gaussians_device).
+// eval: the colour each Gaussian is drawn with under cam (cam_pos and sh_dim alone are read), K1's bit for bit, three floats a
+// row into d_rgb_out -- all n in original order (d_index null, k == n) or row t = Gaussian d_index[t].  select_colour: that
+// colour mapped by q.colour_to_unit into the unit box / ball (splat_colour_query), combined with d_selection by `op` =
+// SPLAT_SEL_OP_*; returns the count selected afterwards.  Both read the scene as a selection does.  recolour: rgb' = A rgb + t
+// (m = 3x4 row-major in host memory) applied to the sh coefficients in place, whole or for distinct indices: edits like an
+// update of sh alone.  Throw what the C calls refuse (a non-finite m among it).
+void eval_colours_device(splat_ctx* ctx, const splat_camera& cam, uint64_t k, const void* d_index, void* d_rgb_out,
+                         void* producer_stream = nullptr);
+uint64_t select_colour_device(splat_ctx* ctx, const splat_colour_query& q, const splat_camera& cam, uint32_t op, void* d_selection,
+                              void* producer_stream = nullptr);
+void recolour_scene_device(splat_ctx* ctx, const float m[12]);
+void recolour_gaussians_device(splat_ctx* ctx, uint64_t k, const void* d_index, const float m[12], void* producer_stream = nullptr);
 // A selection by neighbourhood on the resident scene (splat_select_neighbours_device): Gaussian i passes when the number of OTHER
 // Gaussians of the source set (d_source: n bytes, nonzero = source, null = all) with centres within `radius` of its own lies in
 // [count_min, count_max]; `op` = SPLAT_SEL_OP_* combines that with d_selection (one byte per Gaussian, original index order;

@@ -133,6 +133,15 @@ pub struct SplatSelectQuery {
     pub opacity_min: f32, pub opacity_max: f32,
 }
 
+// a colour query (splat_select_colour_device): a Gaussian passes when colour_to_unit maps the colour it is drawn with into the
+// unit box / ball -- the VOLUME test's semantics in colour space
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct SplatColourQuery {
+    pub colour_to_unit: [f32; 12],                 // 3x4 row-major affine map, colour -> the unit shape
+    pub shape: u32,                                // 0 = box, 1 = ellipsoid
+    pub clamp: u32,                                // nonzero: the colour is clamped to [0, 1] per channel before the map
+}
+
 #[repr(C)] #[derive(Clone, Copy, Default)]
 pub struct SplatRecord {
     pub cx: f32, pub cy: f32, pub hx: f32, pub hy: f32,
@@ -232,6 +241,17 @@ extern "C" {
     pub fn splat_rotate_sh_scene_device(ctx: *mut SplatCtx, r: *const f32) -> c_int;
     pub fn splat_rotate_sh_gaussians_device(ctx: *mut SplatCtx, k: u64, d_index: *const c_void, r: *const f32,
                                             producer_stream: *mut c_void) -> c_int;
+    // colour (added under ABI 7, found by symbol): the colour every Gaussian (d_index null, k == n, original order) or Gaussian
+    // d_index[t] is drawn with under cam (cam_pos and sh_dim alone are read) -- K1's rgb bit for bit, unclamped, three f32 a row
+    // into d_rgb_out; a selection by that colour (op = SPLAT_SEL_OP_*, count_out may be null); and rgb' = A rgb + t (m = 3x4
+    // row-major in HOST memory, every entry finite) applied to the sh coefficients in place -- an edit like an update of sh
+    pub fn splat_eval_colours_device(ctx: *mut SplatCtx, cam: *const SplatCamera, k: u64, d_index: *const c_void, d_rgb_out: *mut c_void,
+                                     producer_stream: *mut c_void) -> c_int;
+    pub fn splat_select_colour_device(ctx: *mut SplatCtx, q: *const SplatColourQuery, cam: *const SplatCamera, op: u32,
+                                      d_selection: *mut c_void, count_out: *mut u64, producer_stream: *mut c_void) -> c_int;
+    pub fn splat_recolour_scene_device(ctx: *mut SplatCtx, m: *const f32) -> c_int;
+    pub fn splat_recolour_gaussians_device(ctx: *mut SplatCtx, k: u64, d_index: *const c_void, m: *const f32,
+                                           producer_stream: *mut c_void) -> c_int;
     // debug / stage parity: the stored order (n u32) and the K1 block bounds (ceil(n/256) x 8 f32); either may be null
     pub fn splat_get_scene_layout(ctx: *mut SplatCtx, orig_out: *mut u32, n: u64, bounds_out: *mut f32, n_blocks: u64) -> c_int;
     pub fn splat_set_slab(ctx: *mut SplatCtx, tile_row0: i32, tile_row1: i32) -> c_int;

@@ -9,7 +9,7 @@ from .camera import Camera  # noqa: F401
 from .gaussians import (GaussianList, DeviceGaussians, naive_gaussians, load_from_ply, synthetic_scene, synthetic_surface_scene,  # noqa: F401
                         synthetic_raw, synthetic_surface_raw, write_ply, trim_ply, ply_layout, inria_layout)
 from .pipelines import GaussianSplatPipeline01, GaussianSplatPipeline02  # noqa: F401
-from .renderer import Renderer, SplatError, sh_rotation_blocks  # noqa: F401
+from .renderer import Renderer, SplatError, sh_rotation_blocks, colour_matrix  # noqa: F401
 from .multi import MultiRenderer, slab_partition_native  # noqa: F401
 
 MODE_EXACT = 0                  # SPLAT_MODE_EXACT: the reference's arithmetic

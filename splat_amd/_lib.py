@@ -59,6 +59,11 @@ class SelectQuery(C.Structure):
                 ("depth_min", C.c_float), ("depth_max", C.c_float), ("opacity_min", C.c_float), ("opacity_max", C.c_float)]
 
 
+class ColourQuery(C.Structure):
+    """splat_colour_query: a Gaussian passes when colour_to_unit maps its colour under the camera into the unit box / ball"""
+    _fields_ = [("colour_to_unit", C.c_float * 12), ("shape", C.c_uint32), ("clamp", C.c_uint32)]
+
+
 # splat_pick_device: its limits, the index of "none" and the one flag of a result
 PICK_MAX_PIXELS, PICK_MAX_HITS, PICK_NONE, PICK_TRUNCATED = 256, 4096, 0xFFFFFFFF, 1
 
@@ -134,6 +139,11 @@ SYMBOLS = [
     ("splat_sh_rotation_blocks", C.c_int, [_fp, _fp, _fp, _fp]),
     ("splat_rotate_sh_scene_device", C.c_int, [C.c_void_p, _fp]),
     ("splat_rotate_sh_gaussians_device", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, _fp, C.c_void_p]),
+    ("splat_eval_colours_device", C.c_int, [C.c_void_p, C.POINTER(CameraC), C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("splat_select_colour_device", C.c_int, [C.c_void_p, C.POINTER(ColourQuery), C.POINTER(CameraC), C.c_uint32, C.c_void_p,
+                                             C.POINTER(C.c_uint64), C.c_void_p]),
+    ("splat_recolour_scene_device", C.c_int, [C.c_void_p, _fp]),
+    ("splat_recolour_gaussians_device", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, _fp, C.c_void_p]),
     ("splat_get_scene_layout", C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint64, _fp, C.c_uint64]),
     ("splat_set_slab", C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
     ("splat_tile_row_loads", C.c_int, [C.c_void_p, C.POINTER(CameraC), C.POINTER(C.c_uint64), C.c_int32]),

@@ -445,6 +445,29 @@ void rotate_sh_gaussians_device(splat_ctx* ctx, uint64_t k, const void* d_index,
     check(splat_rotate_sh_gaussians_device(ctx, k, d_index, r, producer_stream), ctx, "splat_rotate_sh_gaussians_device");
 }
 
+void eval_colours_device(splat_ctx* ctx, const splat_camera& cam, uint64_t k, const void* d_index, void* d_rgb_out, void* producer_stream) {
+    if (!ctx) throw std::runtime_error("eval_colours_device: no context");
+    check(splat_eval_colours_device(ctx, &cam, k, d_index, d_rgb_out, producer_stream), ctx, "splat_eval_colours_device");
+}
+
+uint64_t select_colour_device(splat_ctx* ctx, const splat_colour_query& q, const splat_camera& cam, uint32_t op, void* d_selection,
+                              void* producer_stream) {
+    if (!ctx) throw std::runtime_error("select_colour_device: no context");
+    uint64_t count = 0;
+    check(splat_select_colour_device(ctx, &q, &cam, op, d_selection, &count, producer_stream), ctx, "splat_select_colour_device");
+    return count;
+}
+
+void recolour_scene_device(splat_ctx* ctx, const float m[12]) {
+    if (!ctx) throw std::runtime_error("recolour_scene_device: no context");
+    check(splat_recolour_scene_device(ctx, m), ctx, "splat_recolour_scene_device");
+}
+
+void recolour_gaussians_device(splat_ctx* ctx, uint64_t k, const void* d_index, const float m[12], void* producer_stream) {
+    if (!ctx) throw std::runtime_error("recolour_gaussians_device: no context");
+    check(splat_recolour_gaussians_device(ctx, k, d_index, m, producer_stream), ctx, "splat_recolour_gaussians_device");
+}
+
 uint64_t select_neighbours(splat_ctx* ctx, float radius, const void* d_source, uint32_t count_min, uint32_t count_max, uint32_t op,
                            void* d_selection, void* d_counts_out, uint64_t max_block_pairs, uint64_t* block_pairs_out,
                            void* producer_stream) {

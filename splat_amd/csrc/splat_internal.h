@@ -1,5 +1,6 @@
 // splat_internal.h -- shared between the host files (splat_api.hip, splat_scene.hip) and the kernel files (splat_kernels.hip,
-// splat_ply.hip, splat_ply_encode.hip, splat_update.hip, splat_select.hip, splat_compact.hip, splat_neighbours.hip, splat_pick.hip).
+// splat_ply.hip, splat_ply_encode.hip, splat_update.hip, splat_select.hip, splat_compact.hip, splat_neighbours.hip, splat_pick.hip,
+// splat_colour.hip).
 #ifndef SPLAT_INTERNAL_H
 #define SPLAT_INTERNAL_H
 #include <hip/hip_runtime.h>
@@ -31,6 +32,7 @@
 #endif
 
 struct SplatShBlocks;             // the three sh rotation blocks (splat_sh_math.h)
+struct SplatColourMap;            // a 3x4 map of the colour as the sh coefficients take it (splat_colour_math.h)
 
 namespace splat {
 
@@ -291,6 +293,20 @@ struct PickTemps {
 void launch_pick(hipStream_t s, uint64_t n, const float4* planes, const unsigned int* orig, const unsigned char* mask, const SelectView& v,
                  const splat_pick_query& q, unsigned int n_pixels, const int2* pixels, int4 bound, const PickTemps& t, void* results,
                  void* layers);
+// ... and the colour tools (splat_colour.hip, splat_colour_math.h).  The colour of a Gaussian under the camera position
+// cam_pos at sh_dim, K1's bit for bit: three floats into row orig[j] of out from slot j, or into row t from slot
+// inv[index[t]].  launch_select_colour judges that colour by q (checked) and combines selection[orig[j]] and *count as
+// launch_select_query does.  The recolours apply the map m to the sh of every slot, or of the slots inv[index[t]]; nothing
+// else of a slot changes, so no bounds do.  The indices arrive checked (launch_index_check).
+void launch_eval_colours_scene(hipStream_t s, uint64_t n, const float cam_pos[3], int sh_dim, const unsigned int* orig,
+                               const float4* planes, float* out);
+void launch_eval_colours_indexed(hipStream_t s, uint64_t n, uint64_t k, const unsigned int* index, const float cam_pos[3], int sh_dim,
+                                 const unsigned int* inv, const float4* planes, float* out);
+void launch_select_colour(hipStream_t s, uint64_t n, const float4* planes, const unsigned int* orig, const splat_colour_query& q,
+                          const float cam_pos[3], int sh_dim, uint32_t op, unsigned char* selection, unsigned int* count);
+void launch_recolour_scene(hipStream_t s, uint64_t n, const SplatColourMap& m, float4* planes);
+void launch_recolour_indexed(hipStream_t s, uint64_t n, uint64_t k, const unsigned int* index, const SplatColourMap& m,
+                             const unsigned int* inv, float4* planes);
 
 // ---- The per-frame launches take one argument block each, by const&.  The blocks are plain aggregates without defaults: a
 // caller value-initialises one (`ScanArgs a{};`) and what it does not set is zero / nullptr / false.  What travels together

@@ -3,7 +3,7 @@
 // Gaussians such an edit is for, the removal that takes them out, the append that adds some and the reorder.  Host side only,
 // no device code: the kernels are splat_kernels.hip's (order, bounds, packing), splat_ply.hip's, splat_ply_encode.hip's,
 // splat_update.hip's, splat_transform.hip's, splat_select.hip's, splat_compact.hip's, splat_append.hip's,
-// splat_neighbours.hip's and splat_pick.hip's.
+// splat_neighbours.hip's, splat_pick.hip's and splat_colour.hip's.
 // What the frame scheduler (splat_api.hip) holds per scene is behind the seam of splat_context.h.
 #include <algorithm>
 #include <cmath>
@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "splat_context.h"
+#include "splat_colour_math.h"
 #include "splat_neighbour_math.h"
 #include "splat_sh_math.h"
 
@@ -260,6 +261,22 @@ const char* pick_refusal(const splat_pick_query* q, const splat_camera* cam, uin
     for (uint32_t p = 0; p < n_pixels; ++p)
         if (pixels_xy[2 * p] < 0 || pixels_xy[2 * p] >= W || pixels_xy[2 * p + 1] < 0 || pixels_xy[2 * p + 1] >= H)
             return "pixels_xy: a pixel lies outside [0, w) x [0, h)";
+    return nullptr;
+}
+
+// what the two colour queries refuse before they look at the context or touch HIP; nullptr: nothing
+const char* eval_colours_refusal(const splat_camera* cam, uint64_t k, const void* rgb_out) {
+    if (!cam) return "NULL cam";
+    if (k && !rgb_out) return "NULL d_rgb_out";
+    if (k && ((uintptr_t)rgb_out & 3u)) return "d_rgb_out is misaligned (4 bytes)";
+    return nullptr;
+}
+const char* select_colour_refusal(const splat_colour_query* q, const splat_camera* cam, uint32_t op, const void* selection) {
+    if (!q) return "NULL q";
+    if (!cam) return "NULL cam";
+    if (q->shape > 1u) return "q: unknown shape";
+    if (op > SPLAT_SEL_OP_INTERSECT) return "unknown op";
+    if (!selection) return "NULL d_selection";
     return nullptr;
 }
 
@@ -622,6 +639,97 @@ int splat_rotate_sh_gaussians_device(splat_ctx* c, uint64_t k, const void* d_ind
     HIP_TRY(c, count_bad_indices(c, k, index, &bad));
     if (bad) return fail(c, SPLAT_ERR_INVALID, "an index is not below n; nothing was applied");
     launch_rotate_sh_indexed(c->stream, c->n, k, index, b, c->inv, c->planes);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    scene_edited(c);
+    return SPLAT_OK;
+}
+
+// Colour.  The two queries READ the scene as the selection below does; the two recolours are edits of sh alone, like the
+// rotations above: the map is made on the host (splat_colour_math.h) from an m whose entries and offset are finite, and the
+// bounds stay.  Arguments first, then the context, then what needs the scene's n.
+int splat_eval_colours_device(splat_ctx* c, const splat_camera* cam, uint64_t k, const void* d_index, void* d_rgb_out,
+                              void* producer_stream) {
+    if (const char* why = eval_colours_refusal(cam, k, d_rgb_out)) return fail(c, SPLAT_ERR_INVALID, why);
+    if (!c) return fail(c, SPLAT_ERR_INVALID, "NULL context");
+    if (c->n == 0) return fail(c, SPLAT_ERR_NO_SCENE, "no resident scene to evaluate");
+    if (k > c->n) return fail(c, SPLAT_ERR_INVALID, "k: more rows than Gaussians");
+    if (!d_index && k != c->n) return fail(c, SPLAT_ERR_INVALID, "k is not the resident scene's n (NULL d_index: all Gaussians)");
+    if (k == 0) return SPLAT_OK;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    int rc = ctx_quiesce(c);
+    if (rc != SPLAT_OK) return rc;
+    if (!d_index) {
+        launch_eval_colours_scene(c->stream, c->n, cam->cam_pos, cam->sh_dim, c->orig, c->planes, (float*)d_rgb_out);
+    } else {
+        const unsigned int* index = (const unsigned int*)d_index;
+        HIP_TRY(c, ensure_inverse(c));
+        HIP_TRY(c, follow_producer(c, producer_stream));
+        unsigned int bad = 0;
+        HIP_TRY(c, count_bad_indices(c, k, index, &bad));
+        if (bad) return fail(c, SPLAT_ERR_INVALID, "d_index: an index is not below n; nothing was written");
+        launch_eval_colours_indexed(c->stream, c->n, k, index, cam->cam_pos, cam->sh_dim, c->inv, c->planes, (float*)d_rgb_out);
+    }
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SPLAT_OK;
+}
+
+int splat_select_colour_device(splat_ctx* c, const splat_colour_query* q, const splat_camera* cam, uint32_t op, void* d_selection,
+                               uint64_t* count_out, void* producer_stream) {
+    if (const char* why = select_colour_refusal(q, cam, op, d_selection)) return fail(c, SPLAT_ERR_INVALID, why);
+    if (!c) return fail(c, SPLAT_ERR_INVALID, "NULL context");
+    if (c->n == 0) return fail(c, SPLAT_ERR_NO_SCENE, "no resident scene to select from");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    int rc = ctx_quiesce(c);
+    if (rc != SPLAT_OK) return rc;
+    Temps t(c);
+    unsigned int* d_count = nullptr;
+    unsigned int count = 0;
+    HIP_TRY(c, t.alloc(&d_count, sizeof(unsigned int)));
+    HIP_TRY(c, hipMemsetAsync(d_count, 0, sizeof(unsigned int), c->stream));
+    HIP_TRY(c, follow_producer(c, producer_stream));
+    launch_select_colour(c->stream, c->n, c->planes, c->orig, *q, cam->cam_pos, cam->sh_dim, op, (unsigned char*)d_selection, d_count);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(&count, d_count, sizeof count, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (count_out) *count_out = count;
+    return SPLAT_OK;
+}
+
+int splat_recolour_scene_device(splat_ctx* c, const float m[12]) {
+    if (!m) return fail(c, SPLAT_ERR_INVALID, "NULL m");
+    SplatColourMap map;
+    if (const char* why = recolour_map(m, map)) return fail(c, SPLAT_ERR_INVALID, why);
+    if (!c) return fail(c, SPLAT_ERR_INVALID, "NULL context");
+    if (c->n == 0) return fail(c, SPLAT_ERR_NO_SCENE, "no resident scene to recolour");
+    int rc = end_frames_for_edit(c);
+    if (rc != SPLAT_OK) return rc;
+    launch_recolour_scene(c->stream, c->n, map, c->planes);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    scene_edited(c);
+    return SPLAT_OK;
+}
+
+int splat_recolour_gaussians_device(splat_ctx* c, uint64_t k, const void* d_index, const float m[12], void* producer_stream) {
+    if (!m) return fail(c, SPLAT_ERR_INVALID, "NULL m");
+    SplatColourMap map;
+    if (const char* why = recolour_map(m, map)) return fail(c, SPLAT_ERR_INVALID, why);
+    if (k && !d_index) return fail(c, SPLAT_ERR_INVALID, "NULL d_index");
+    if (!c) return fail(c, SPLAT_ERR_INVALID, "NULL context");
+    if (c->n == 0) return fail(c, SPLAT_ERR_NO_SCENE, "no resident scene to recolour");
+    if (k > c->n) return fail(c, SPLAT_ERR_INVALID, "k: more indices than Gaussians: they cannot be distinct");
+    if (k == 0) return SPLAT_OK;
+    int rc = end_frames_for_edit(c);
+    if (rc != SPLAT_OK) return rc;
+    const unsigned int* index = (const unsigned int*)d_index;
+    HIP_TRY(c, ensure_inverse(c));
+    HIP_TRY(c, follow_producer(c, producer_stream));
+    unsigned int bad = 0;
+    HIP_TRY(c, count_bad_indices(c, k, index, &bad));
+    if (bad) return fail(c, SPLAT_ERR_INVALID, "d_index: an index is not below n; nothing was applied");
+    launch_recolour_indexed(c->stream, c->n, k, index, map, c->inv, c->planes);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     scene_edited(c);

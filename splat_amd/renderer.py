@@ -109,6 +109,28 @@ def sh_rotation_blocks(rotation):
     return tuple(d)
 
 
+LUMA = (0.2126, 0.7152, 0.0722)                      # Rec. 709 weights of linear r, g, b
+
+
+def colour_matrix(saturation=1.0, tint=(1.0, 1.0, 1.0), contrast=1.0, brightness=0.0):
+    """A 3x4 float32 colour map [A | t] (rgb' = A rgb + t) for Renderer.recolour, built in float64 in this order:
+    1. saturation s: A = s I + (1 - s) 1 w^T with w = LUMA (0: every channel becomes the luma, 1: nothing changes);
+    2. tint: A <- diag(tint) A;
+    3. contrast c about 0.5: A <- c A, t <- c t + 0.5 (1 - c);
+    4. brightness b: t <- t + b.
+    The defaults give the identity exactly.  Host only: needs neither a Renderer nor a GPU."""
+    s, c, b = float(saturation), float(contrast), float(brightness)
+    tint = np.asarray(tint, np.float64).reshape(-1)
+    if tint.size != 3:
+        raise ValueError("tint: 3 numbers expected, got %d" % tint.size)
+    A = s * np.eye(3) + (1.0 - s) * np.outer(np.ones(3), np.asarray(LUMA, np.float64))
+    t = np.zeros(3)
+    A = np.diag(tint) @ A
+    A, t = c * A, c * t + 0.5 * (1.0 - c)
+    t = t + b
+    return np.concatenate([A, t[:, None]], 1).astype(f32)
+
+
 class Renderer:
     """One context = one GPU = one stream.  `conventions` overrides splat_default_config fields
     (y_up, sample_half, zclip, zmin, zmax)."""
@@ -292,6 +314,130 @@ class Renderer:
 
     # ---- selections ---------------------------------------------------------------------
     _SEL_OPS = {"set": _lib.SEL_OP_SET, "add": _lib.SEL_OP_ADD, "subtract": _lib.SEL_OP_SUBTRACT, "intersect": _lib.SEL_OP_INTERSECT}
+
+    # ---- colour ---------------------------------------------------------------------------
+    def _indices(self, index, k):
+        """(k, address, address to free or 0) of 32-bit indices: device memory as _index_address takes it, or a host sequence
+        of integers, which is copied into a buffer of the call's own"""
+        if isinstance(index, int) or hasattr(index, "data_ptr"):
+            return self._index_address(index, k) + (0,)
+        host = np.ascontiguousarray(index)
+        if host.size and host.dtype.kind not in "iu":
+            raise TypeError("idx: integer indices expected, got %s" % host.dtype)
+        if host.size and (host.min() < 0 or host.max() > 0xFFFFFFFF):
+            raise ValueError("idx: indices are 32-bit and not negative")
+        host = np.ascontiguousarray(host.reshape(-1), np.uint32)
+        if not host.size:
+            return 0, 0, 0
+        p = self._L.splat_device_alloc(self._h, host.nbytes)
+        if not p:
+            raise SplatError(_lib.ERR_HIP, (self._L.splat_last_error(self._h) or b"no device memory for the indices").decode())
+        rc = self._L.splat_device_upload(self._h, C.c_void_p(p), C.c_void_p(host.ctypes.data), host.nbytes)
+        if rc != 0:
+            self.device_free(p)
+            self._check(rc)
+        return int(host.size), p, p
+
+    def colours(self, cam_c, idx=None, out=None, stream=None, k=None):
+        """splat_eval_colours_device: the colour each Gaussian is drawn with under cam_c -- eval_sh at the direction from
+        cam_c.cam_pos, bands as cam_c.sh_dim names them, + 0.5, unclamped: the r, g, b of the records a frame of cam_c is made
+        of, bit for bit, for every Gaussian, visible or not (a NaN stays a NaN).  idx=None: all n, original index order.
+        Otherwise row t belongs to Gaussian idx[t]: 32-bit indices in device memory (a device address with k=, or an object
+        with data_ptr()) or a host sequence of integers, in any order, duplicates allowed.  out=None: returns a numpy float32
+        array [k, 3].  With out= (device memory of 3 k float32: an address or an object with data_ptr()) the call writes
+        there, copies nothing down and returns out.  Reads the scene only, as select does.  An index >= n raises
+        SplatError(ERR_INVALID) with nothing written."""
+        if idx is None:
+            k, pi, mine = self.n, 0, 0
+        else:
+            k, pi, mine = self._indices(idx, k)
+        own = 0
+        try:
+            if k == 0 and idx is not None:                     # no rows: nothing is asked of the library
+                return np.zeros((0, 3), f32) if out is None else out
+            if out is None:
+                own = po = self._L.splat_device_alloc(self._h, 12 * k)
+                if not po:
+                    raise SplatError(_lib.ERR_HIP, (self._L.splat_last_error(self._h) or b"no device memory for the colours").decode())
+            else:
+                po = _device_address(out, "out", 3 * k, int(self.config.device))
+            st = _producer_stream(stream, (idx, out))
+            self._check(self._L.splat_eval_colours_device(self._h, C.byref(cam_c) if cam_c is not None else None, k,
+                                                          C.c_void_p(pi) if idx is not None else None, C.c_void_p(po), C.c_void_p(st)))
+            if out is not None:
+                return out
+            rgb = np.zeros((k, 3), f32)
+            self._check(self._L.splat_device_download(self._h, C.c_void_p(rgb.ctypes.data), C.c_void_p(po), rgb.nbytes))
+            return rgb
+        finally:
+            for p in (own, mine):
+                if p:
+                    self.device_free(p)
+
+    def select_colour(self, cam_c, selection, rgb=None, tolerance=None, matrix=None, shape="ellipsoid", clamp=True, op="set",
+                      stream=None):
+        """splat_select_colour_device, the magic wand: which Gaussians are drawn, under cam_c, in a colour that a 3x4 map takes
+        into the unit box (shape="box": |u_k| <= 1) or the unit ball (shape="ellipsoid": |u|^2 <= 1), into `selection` (as
+        select takes it), combined by op.  rgb= and tolerance= (a scalar or a per-channel triple): the colours within
+        `tolerance` of rgb -- colour_to_unit = [diag(1 / tolerance) | -rgb / tolerance], made in float64 and rounded to
+        float32; matrix=: the map itself (3x4: a luminance band is one row of luma weights and two zero rows).  clamp: the
+        colour is clamped to [0, 1] per channel first, as a frame's bytes show it.  A NaN colour never passes.  Returns how
+        many Gaussians are selected after the op."""
+        if shape not in ("box", "ellipsoid"):
+            raise ValueError("shape: 'box' or 'ellipsoid', got %r" % (shape,))
+        if op not in self._SEL_OPS:
+            raise ValueError("op: one of %s, got %r" % (sorted(self._SEL_OPS), op))
+        if matrix is not None:
+            if rgb is not None or tolerance is not None:
+                raise ValueError("matrix= or rgb= with tolerance=: one of the two")
+            m = np.asarray(matrix, dtype=f32)
+            if m.size != 12:
+                raise ValueError("matrix: 12 (3x4) numbers expected, got %d" % m.size)
+        else:
+            if rgb is None or tolerance is None:
+                raise ValueError("rgb= and tolerance= go together (or give matrix=)")
+            c = np.asarray(rgb, np.float64).reshape(-1)
+            if c.size != 3:
+                raise ValueError("rgb: 3 numbers expected, got %d" % c.size)
+            tol = np.asarray(tolerance, np.float64).reshape(-1)
+            if tol.size not in (1, 3):
+                raise ValueError("tolerance: a scalar or 3 numbers expected, got %d" % tol.size)
+            tol = np.broadcast_to(tol, (3,))
+            if not (tol > 0).all():
+                raise ValueError("tolerance: positive numbers expected, got %r" % (tolerance,))
+            m = np.concatenate([np.diag(1.0 / tol), (-c / tol)[:, None]], 1).astype(f32)
+        q = _lib.ColourQuery()
+        q.colour_to_unit[:] = [float(x) for x in np.ascontiguousarray(m, f32).ravel()]
+        q.shape = 0 if shape == "box" else 1
+        q.clamp = 1 if clamp else 0
+        ps = _byte_mask_address(selection, "selection", self.n, int(self.config.device))
+        st = _producer_stream(stream, (selection,))
+        count = C.c_uint64()
+        self._check(self._L.splat_select_colour_device(self._h, C.byref(q), C.byref(cam_c) if cam_c is not None else None,
+                                                       self._SEL_OPS[op], C.c_void_p(ps), C.byref(count), C.c_void_p(st)))
+        return int(count.value)
+
+    def recolour(self, m, idx=None, stream=None, k=None):
+        """splat_recolour_scene_device / splat_recolour_gaussians_device: the colour map rgb' = A rgb + t (m = [A | t]: anything
+        that reshapes to 3x4, cast to float32; colour_matrix makes one) applied to what every Gaussian is drawn with, from
+        every direction and at every sh_dim, by mapping its sh coefficients in place -- for the whole scene or for the
+        Gaussians idx[0..k) (distinct; device memory as in update_indexed, or a host sequence of integers).  Every other field
+        keeps its bits.  A non-finite entry raises SplatError(ERR_INVALID) with nothing applied.  An edit like update_device
+        of sh alone."""
+        a = np.asarray(m, dtype=f32)
+        if a.size != 12:
+            raise ValueError("m: 12 (3x4) numbers expected, got %d" % a.size)
+        a = np.ascontiguousarray(a.reshape(12), f32)
+        if idx is None:
+            self._check(self._L.splat_recolour_scene_device(self._h, _fp(a)))
+            return
+        k, pi, mine = self._indices(idx, k)
+        try:
+            st = _producer_stream(stream, (idx,))
+            self._check(self._L.splat_recolour_gaussians_device(self._h, k, C.c_void_p(pi), _fp(a), C.c_void_p(st)))
+        finally:
+            if mine:
+                self.device_free(mine)
 
     def select(self, selection, cam_c=None, *, box=None, ellipsoid=None, rect=None, rule="centre", pixel_mask=None, depth=None,
                opacity=None, op="set", stream=None):
