@@ -49,7 +49,8 @@ extern "C" {
  * splat_remove_gaussians_device (and the SPLAT_REMOVE_* values it takes), and
  * splat_append_gaussians_device and splat_reorder_scene_device, and
  * splat_eval_colours_device, splat_select_colour_device (and the splat_colour_query it takes), splat_recolour_scene_device
- * and splat_recolour_gaussians_device. */
+ * and splat_recolour_gaussians_device, and
+ * splat_visibility_device (and the splat_visibility_query and SPLAT_VIS_* values it takes) and splat_select_counts_device. */
 
 /* modes: bit flags, 0 = the default */
 #define SPLAT_MODE_EXACT 0       /* back-to-front, 8-bit truncation per splat as blend() does it; the exponential of
@@ -413,6 +414,57 @@ typedef struct {
 } splat_pick_layer;
 int splat_pick_device(splat_ctx* ctx, const splat_pick_query* q, const splat_camera* cam, uint32_t n_pixels,
                       const int32_t* pixels_xy, const void* d_mask, void* d_results, void* d_layers, void* producer_stream);
+
+/* VISIBILITY: what each Gaussian contributes to a view, occlusion taken into account -- for every Gaussian, on how many pixels
+ * of a region of `cam`'s WHOLE target it is really SEEN, and how much.  The primitive behind "select what is seen under the
+ * brush" and behind contribution-based pruning over a set of cameras.  Everything is exact: integers and f32 bit patterns.
+ *   Hits      The hits of a pixel and their order are splat_pick_device's with alpha_min = 0 (above): the same record, the same
+ *             rectangle test, the same fragment with glibc's expf whatever mode the context renders in, nearest first.  A
+ *             Gaussian whose byte of d_mask (nullable; n bytes, ORIGINAL index order) is 0 does not exist for the query: it is
+ *             neither counted nor occluding.  Conventions, projection mode and "a slab is ignored" are the pick's.
+ *   Weights   Walking a pixel's hits nearest first with T_0 = 1:  w_k = T_{k-1} * alpha_k (one rounded f32 product), then
+ *             T_k = T_{k-1} * (1 - alpha_k) (the subtraction rounded, then the product: the pick's chain).  Hit k is SEEN at
+ *             the pixel when w_k >= weight_min.  T never increases and w_k <= T_{k-1}, so with weight_min > 0 a pixel stops
+ *             as soon as T < weight_min -- exactly, nothing is lost; with weight_min == 0 the whole list is walked.
+ *   Outputs   per Gaussian i, over the pixels of the region where it is seen, into the caller's DEVICE arrays of n entries,
+ *             ORIGINAL index order, each nullable (not all three):
+ *               d_pixels      uint32   how many pixels
+ *               d_max_weight  float    the greatest w (0 if none); 4-byte aligned like d_pixels
+ *               d_weight_sum  uint64   the sum of (uint32_t)(w * 16777216.0f), truncating: Q24 fixed point, so that the sum
+ *                                      does not depend on the order the pixels arrive in; 8-byte aligned
+ *   Region    the inclusive pixel rectangle [x0, x1] x [y0, y1], clamped to the target (empty: nothing is done), and with
+ *             d_pixel_mask (nullable; w * h bytes, row-major, as the SCREEN test takes it) the pixels whose byte is nonzero.
+ *   op        SPLAT_VIS_SET zeroes the given arrays first; SPLAT_VIS_ACCUMULATE adds (pixels, weight_sum) and maxes
+ *             (max_weight, which must hold non-negative floats) on top of what they hold: a loop over cameras leaves the
+ *             importance of every Gaussian over the view set on the device.
+ * Synchronous, on the context's stream behind the frames in flight (producer_stream: the stream that wrote the masks and,
+ * with ACCUMULATE, the arrays).  It READS the scene's values; it BINS the view like a two-pass frame does, into the first
+ * frame slot's records and tile tables: frames rendered afterwards are byte for byte the frames they would have been, but
+ * lists retained for a camera at rest and the tiles' region layouts start over (time only).  splat_device_bytes() may grow
+ * by what the two-pass path keeps per Gaussian in that slot (16 bytes a Gaussian, made once) and, for a target of more
+ * tiles than any before it, by the per-tile tables; the call's own key buffers (8 bytes per (Gaussian, tile) pair, and a mirror of as
+ * many only where a tile's list exceeds 16384 keys) are freed.
+ * SPLAT_ERR_INVALID, judged before the context is looked at, splat_last_error names the argument: a NULL q or cam, weight_min
+ * NaN, negative or >= 1, an unknown op, a target that is no integer size in [1, 65535], a misaligned output, all three outputs
+ * NULL.  Then a NULL context: SPLAT_ERR_INVALID; no resident scene: SPLAT_ERR_NO_SCENE.  An empty region: SPLAT_OK with
+ * nothing written beyond what SET zeroes.  The multi-GPU layer needs no counterpart: every rank holds the whole scene.
+ *
+ * splat_select_counts_device turns such counts (or any n uint32 in device memory, 4-byte aligned) into a selection:
+ * Gaussian i passes when count_min <= d_counts[i] <= count_max, combined with d_selection (n bytes) by `op`
+ * (SPLAT_SEL_OP_*); *count_out (nullable) = the Gaussians selected afterwards.  It needs no scene.  SPLAT_ERR_INVALID, before
+ * the context is looked at: count_min above count_max, an unknown op, n >= 2^32, with n > 0 a NULL or misaligned d_counts or
+ * a NULL d_selection; then a NULL context.  n == 0: SPLAT_OK, *count_out = 0. */
+#define SPLAT_VIS_SET        0u
+#define SPLAT_VIS_ACCUMULATE 1u
+typedef struct {
+    float    weight_min;       /* a hit is seen when its weight is at least this; in [0, 1) */
+    int32_t  x0, y0, x1, y1;   /* the region's rectangle, inclusive; clamped to the target */
+    uint32_t op;               /* SPLAT_VIS_* */
+} splat_visibility_query;
+int splat_visibility_device(splat_ctx* ctx, const splat_visibility_query* q, const splat_camera* cam, const void* d_pixel_mask,
+                            const void* d_mask, void* d_pixels, void* d_max_weight, void* d_weight_sum, void* producer_stream);
+int splat_select_counts_device(splat_ctx* ctx, uint64_t n, const void* d_counts, uint32_t count_min, uint32_t count_max,
+                               uint32_t op, void* d_selection, uint64_t* count_out, void* producer_stream);
 
 /* Gaussians TAKEN OUT of the resident scene -- delete what is selected, or crop to it -- with the survivors compacted where
  * they lie: nothing crosses PCIe but one count, nothing is sorted (the survivors of a Morton-ordered scene are Morton-ordered),

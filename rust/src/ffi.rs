@@ -92,6 +92,16 @@ pub struct SplatPlyLayout {
     pub n: u64, pub stride: u32, pub offset: [i32; SPLAT_PLY_SLOTS],
 }
 
+// the visibility query: what it does with the output arrays, and its 24-byte layout
+pub const SPLAT_VIS_SET: u32 = 0;
+pub const SPLAT_VIS_ACCUMULATE: u32 = 1;
+#[repr(C)] #[derive(Clone, Copy, Default)]
+pub struct SplatVisibilityQuery {
+    pub weight_min: f32,                           // a hit is seen when its weight is at least this; in [0, 1)
+    pub x0: i32, pub y0: i32, pub x1: i32, pub y1: i32,    // the region's rectangle, inclusive; clamped to the target
+    pub op: u32,                                   // SPLAT_VIS_*
+}
+
 // the pick: its limits, the index of "none", the one flag of a result, and the three layouts (16, 32 and 16 bytes)
 pub const SPLAT_PICK_MAX_PIXELS: u32 = 256;
 pub const SPLAT_PICK_MAX_HITS: u32 = 4096;
@@ -208,6 +218,18 @@ extern "C" {
     pub fn splat_pick_device(ctx: *mut SplatCtx, q: *const SplatPickQuery, cam: *const SplatCamera, n_pixels: u32,
                              pixels_xy: *const i32, d_mask: *const c_void, d_results: *mut c_void, d_layers: *mut c_void,
                              producer_stream: *mut c_void) -> c_int;
+    // ... and the visibility query (added under ABI 7, found by symbol): per Gaussian, on how many pixels of the region of cam's
+    // target it is SEEN (weight T * alpha >= weight_min on the pick's hit list, nearest first), its greatest weight and the Q24
+    // sum of its weights, into d_pixels (n u32), d_max_weight (n f32), d_weight_sum (n u64): device memory, each may be null, not
+    // all; d_pixel_mask (w * h bytes) and d_mask (n bytes like a selection) may be null; q.op: SPLAT_VIS_SET zeroes first,
+    // SPLAT_VIS_ACCUMULATE adds and maxes on top -- a loop over cameras
+    pub fn splat_visibility_device(ctx: *mut SplatCtx, q: *const SplatVisibilityQuery, cam: *const SplatCamera,
+                                   d_pixel_mask: *const c_void, d_mask: *const c_void, d_pixels: *mut c_void,
+                                   d_max_weight: *mut c_void, d_weight_sum: *mut c_void, producer_stream: *mut c_void) -> c_int;
+    // ... and counts turned into a selection: Gaussian i passes when count_min <= d_counts[i] <= count_max (n u32 in device
+    // memory), combined with d_selection (n bytes) by op = SPLAT_SEL_OP_*; needs no scene; count_out may be null
+    pub fn splat_select_counts_device(ctx: *mut SplatCtx, n: u64, d_counts: *const c_void, count_min: u32, count_max: u32, op: u32,
+                                      d_selection: *mut c_void, count_out: *mut u64, producer_stream: *mut c_void) -> c_int;
     // ... and Gaussians taken out of the scene by a selection (added under ABI 7, found by symbol): mode = SPLAT_REMOVE_*;
     // d_selection = n bytes like a selection, n the resident scene's; *n_out (required) = the survivors, renumbered by their rank
     // in original index order; d_index_map_out (n u32, may be null): the new index of every old Gaussian, or 0xFFFF_FFFF

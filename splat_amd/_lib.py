@@ -84,6 +84,16 @@ class PickLayer(C.Structure):
     _fields_ = [("index", C.c_uint32), ("depth", C.c_float), ("alpha", C.c_float), ("coverage", C.c_float)]
 
 
+# splat_visibility_device: what it does with the output arrays
+VIS_SET, VIS_ACCUMULATE = 0, 1
+
+
+class VisibilityQuery(C.Structure):
+    """splat_visibility_query: a hit is seen when its weight is at least weight_min, on the pixels of the inclusive rectangle"""
+    _fields_ = [("weight_min", C.c_float), ("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32), ("y1", C.c_int32),
+                ("op", C.c_uint32)]
+
+
 PLY_SLOTS = 59
 # destination slots of splat_ply_layout.offset: (first slot, count) per buffer, and the PLY property that feeds each slot
 PLY_SLOT_POS, PLY_SLOT_SCALE, PLY_SLOT_OPACITY, PLY_SLOT_ROT, PLY_SLOT_SH = 0, 3, 6, 7, 11
@@ -126,6 +136,10 @@ SYMBOLS = [
                                                  C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]),
     ("splat_pick_device", C.c_int, [C.c_void_p, C.POINTER(PickQuery), C.POINTER(CameraC), C.c_uint32, C.POINTER(C.c_int32), C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("splat_visibility_device", C.c_int, [C.c_void_p, C.POINTER(VisibilityQuery), C.POINTER(CameraC), C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("splat_select_counts_device", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                             C.POINTER(C.c_uint64), C.c_void_p]),
     ("splat_remove_gaussians_device", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64),
                                                 C.c_void_p]),
     ("splat_append_gaussians_device", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

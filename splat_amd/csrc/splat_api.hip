@@ -1446,6 +1446,78 @@ void scene_installed(splat_ctx* c, uint64_t n) {
         if ((want + want2) * 8ull * (uint64_t)slots_in_use(c) <= c->bucket_bytes && ensure_keys(c, want, want2) != SPLAT_OK) (void)hipGetLastError();
     }
 }
+// A view's tile lists for a scene query, outside any frame: what splat_tile_row_loads does (K1's counting flavour and the scan
+// into slot 0, the slab ignored), then -- the pair count and the list-length classes read back -- the emit into key buffers
+// sized exactly and the sort launches with every list of two keys or more in them (fused_sort_max = 0: the short ones too;
+// the grids are the scan's own prefixes of the longest-first order).  No block culling: a query wants every record K1 makes.
+int bin_view_for_query(splat_ctx* c, const splat_camera* cam, ViewLists* out) {
+    *out = ViewLists{};
+    int rc = finish_quiet(c);
+    if (rc != SPLAT_OK) return rc;
+    const int s0 = c->slab0, s1 = c->slab1;
+    c->slab0 = 0; c->slab1 = -1;
+    FrameConst fc; unsigned int nt = 0;
+    rc = build_frame_const(c, cam, &fc, &nt);
+    c->slab0 = s0; c->slab1 = s1;
+    if (rc != SPLAT_OK) return rc;
+    fc.bucket_cap = 0; fc.cull_blocks = 0;
+    out->fc = fc; out->n_tiles = nt;
+    if (c->n == 0 || nt == 0) return SPLAT_OK;
+    rc = ensure_bins(c, nt);
+    if (rc != SPLAT_OK) return rc;
+    Slot& s = c->slots[0];
+    rc = ensure_two_pass_buffers(c, s);
+    if (rc != SPLAT_OK) return rc;
+    bump_epoch(c);              // (the pass below writes the slot's records, tile table and counters)
+    HIP_TRY(c, hipMemsetAsync(s.counts, 0, sizeof(unsigned int) * ((size_t)nt + 1), c->stream));   // (one-pass frames leave cursors there)
+    s.layout_valid = false; s.flip = 0;                                                          // ... and will find them gone
+    HIP_TRY(c, hipMemsetAsync(s.d_status, 0, sizeof(FrameStatus), c->stream));
+    BinArgs k1{};       // (the counting flavour: no bounds, no block words, no layout, no keys)
+    k1.s = c->stream; k1.knobs = &c->knobs; k1.scene = {c->n, c->planes, c->orig, nullptr}; k1.fc = fc; k1.recs = s.recs; k1.depth = s.depth;
+    k1.rect = s.rect; k1.vislist = s.vislist; k1.bin.cursors = s.counts; k1.status = s.d_status;
+    launch_preprocess(k1);
+    const TileLists lists = {s.offsets, s.order, s.lens, s.cursor, nullptr, nullptr};
+    ScanArgs scan{};
+    scan.s = c->stream; scan.knobs = &c->knobs; scan.m = nt; scan.bin = k1.bin; scan.lists = lists;
+    scan.keys.cap = ~0ull; scan.grids = {nt, nt, nt}; scan.status = s.d_status;
+    launch_scan(scan);
+    HIP_TRY(c, hipGetLastError());
+    FrameStatus st{};
+    HIP_TRY(c, hipMemcpyAsync(&st, s.d_status, sizeof st, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (st.overflow != 0 || st.n_pairs >= KEY_ENTRIES_MAX) {
+        (void)hipMemsetAsync(s.d_status, 0, sizeof(FrameStatus), c->stream);
+        return fail(c, SPLAT_ERR_CAPACITY, "the view has more (Gaussian, tile) pairs than a key buffer can index");
+    }
+    if (st.n_pairs != 0) {
+        hipError_t e = dmalloc(c, &out->keys, sizeof(unsigned long long) * st.n_pairs);
+        // (the second buffer mirrors the first, list for list: the run merges and global radix passes of lists beyond 16384 keys)
+        if (e == hipSuccess && st.max_tile_len > 16384u) e = dmalloc(c, &out->keys2, sizeof(unsigned long long) * st.n_pairs);
+        if (e != hipSuccess) {
+            dfree(out->keys); dfree(out->keys2);
+            (void)hipMemsetAsync(s.d_status, 0, sizeof(FrameStatus), c->stream);
+            return fail(c, SPLAT_ERR_HIP, std::string("hipMalloc(query key buffers): ") + hipGetErrorString(e));
+        }
+        EmitArgs emit{};
+        emit.s = c->stream; emit.scene = scene_of(c); emit.fc = fc; emit.depth = s.depth; emit.rect = s.rect; emit.vislist = s.vislist;
+        emit.cursor = s.cursor; emit.keys = out->keys; emit.status = s.d_status;
+        launch_emit(emit);
+        SortArgs sort{};
+        sort.s = c->stream; sort.knobs = &c->knobs; sort.n_tiles = nt; sort.grids = {st.n_ge8192, st.n_ge2048, st.n_ge16384};
+        sort.lists = lists; sort.keys.keys = out->keys; sort.keys.keys2 = out->keys2; sort.status = s.d_status; sort.orig = c->orig;
+        sort.fused_sort_max = 0u;
+        launch_sort(sort);
+    }
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemsetAsync(s.d_status, 0, sizeof(FrameStatus), c->stream);     // frames expect a zeroed status
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(c->stream);
+        dfree(out->keys); dfree(out->keys2);
+        return fail(c, SPLAT_ERR_HIP, std::string("the query's binning: ") + hipGetErrorString(e));
+    }
+    out->recs = s.recs; out->rect = s.rect; out->offsets = s.offsets; out->lens = s.lens; out->n_pairs = st.n_pairs;
+    return SPLAT_OK;
+}
 }  // namespace splat
 
 extern "C" {

@@ -108,6 +108,17 @@ int end_frames_for_upload(splat_ctx* c);     // the scene is being replaced: its
 int end_frames_for_edit(splat_ctx* c);       // the scene is being edited: its frames end; one found skipped stays pending for splat_sync
 void scene_edited(splat_ctx* c);             // other values under every tile: what the scheduler learnt from the old ones goes
 void scene_installed(splat_ctx* c, uint64_t n);   // another scene of n Gaussians: scene_edited, and the per-tile arrays and key buffers exist
+// A scene query that needs a view's tile lists (splat_visibility_device): the view binned like a two-pass frame over the whole
+// target -- the frames in flight ended first, a slab ignored -- into the first frame slot's records and tile tables, every list
+// in blend order in key buffers of the call's own: keys (and keys2, made only where a list needs it) are the CALLER's to
+// dfree; nullptr with n_pairs == 0.  Everything is enqueued on the context's stream; the slot's counters and status are left
+// zeroed, as frames expect them.
+struct ViewLists {
+    FrameConst fc; unsigned int n_tiles;
+    const Rec* recs; const ushort4* rect; const unsigned int *offsets, *lens;
+    unsigned long long *keys, *keys2; uint64_t n_pairs;
+};
+int bin_view_for_query(splat_ctx* c, const splat_camera* cam, ViewLists* out);
 // ... and what the scheduler asks of the scene
 void free_scene(splat_ctx* c);               // the scene's buffers and the frame slots' per-Gaussian ones go; n = 0
 int ensure_h_orig(splat_ctx* c);             // c->h_orig holds the scene's order (the debug getters translate slots with it)

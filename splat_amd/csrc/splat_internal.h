@@ -1,6 +1,6 @@
 // splat_internal.h -- shared between the host files (splat_api.hip, splat_scene.hip) and the kernel files (splat_kernels.hip,
 // splat_ply.hip, splat_ply_encode.hip, splat_update.hip, splat_select.hip, splat_compact.hip, splat_neighbours.hip, splat_pick.hip,
-// splat_colour.hip).
+// splat_colour.hip, splat_visibility.hip).
 #ifndef SPLAT_INTERNAL_H
 #define SPLAT_INTERNAL_H
 #include <hip/hip_runtime.h>
@@ -432,6 +432,21 @@ struct CompositeArgs {
     unsigned long long* stage_mask; // and leave for the next -- 4 words / 4 x 32 masks per tile (CompArgs); nullptr: none kept
 };
 void launch_composite(const CompositeArgs& a);
+
+// What each Gaussian contributes to a view (splat_visibility.hip), behind K1's counting flavour, the scan, the emit and the sort
+// launches of a two-pass binning over the WHOLE target with every list in order: offsets / lens / keys are its tile lists (keys
+// carry slots, blend order: a list's far end is the nearest), recs / rect its records and covered rectangles in slot order.
+// The region arrives checked: x0 <= x1 and y0 <= y1 inside the target, or empty (nothing is launched); pixel_mask: W * H bytes
+// or nullptr; mask: one byte per Gaussian, ORIGINAL index order, or nullptr.  The three outputs (n entries each, ORIGINAL index
+// order, each nullable) are ADDED to (pixels, weight_sum) and MAXED (max_weight, by its bits): the caller zeroes them for a SET.
+struct VisibilityArgs {
+    hipStream_t s; int W, tiles_x, y_up, sample_half;
+    int x0, y0, x1, y1; float weight_min;
+    const unsigned int *offsets, *lens; const unsigned long long* keys; const Rec* recs; const ushort4* rect; const unsigned int* orig;
+    const unsigned char *mask, *pixel_mask;
+    unsigned int* pixels; float* max_weight; unsigned long long* weight_sum;
+};
+void launch_visibility(const VisibilityArgs& a);
 // a frame composited from retained lists: its device status starts from these values (no scan ran to initialise it)
 void launch_status_set(hipStream_t s, FrameStatus* status, const FrameStatus& v);
 hipError_t init_device_kernels();   // per-device kernel attributes; call with the device current

@@ -3,7 +3,7 @@
 // Gaussians such an edit is for, the removal that takes them out, the append that adds some and the reorder.  Host side only,
 // no device code: the kernels are splat_kernels.hip's (order, bounds, packing), splat_ply.hip's, splat_ply_encode.hip's,
 // splat_update.hip's, splat_transform.hip's, splat_select.hip's, splat_compact.hip's, splat_append.hip's,
-// splat_neighbours.hip's, splat_pick.hip's and splat_colour.hip's.
+// splat_neighbours.hip's, splat_pick.hip's, splat_colour.hip's and splat_visibility.hip's.
 // What the frame scheduler (splat_api.hip) holds per scene is behind the seam of splat_context.h.
 #include <algorithm>
 #include <cmath>
@@ -48,6 +48,10 @@ struct Temps {
         T* q = p;
         p = nullptr;
         return q;
+    }
+    template <typename T>
+    void adopt(T* p) {                         // made elsewhere (dmalloc), freed here
+        if (p) bufs.push_back((void*)p);
     }
     hipError_t event(hipEvent_t* e) {          // (with timing)
         hipError_t err = hipEventCreate(e);
@@ -261,6 +265,32 @@ const char* pick_refusal(const splat_pick_query* q, const splat_camera* cam, uin
     for (uint32_t p = 0; p < n_pixels; ++p)
         if (pixels_xy[2 * p] < 0 || pixels_xy[2 * p] >= W || pixels_xy[2 * p + 1] < 0 || pixels_xy[2 * p + 1] >= H)
             return "pixels_xy: a pixel lies outside [0, w) x [0, h)";
+    return nullptr;
+}
+
+// what splat_visibility_device and splat_select_counts_device refuse before they look at the context or touch HIP; nullptr: nothing
+const char* visibility_refusal(const splat_visibility_query* q, const splat_camera* cam, const void* pixels, const void* max_weight,
+                               const void* weight_sum) {
+    if (!q) return "NULL q";
+    if (!cam) return "NULL cam";
+    if (!(q->weight_min >= 0.0f) || !(q->weight_min < 1.0f)) return "q: weight_min is not in [0, 1)";
+    if (q->op > SPLAT_VIS_ACCUMULATE) return "q: unknown op";
+    if (!(cam->w >= 1.0f) || !(cam->h >= 1.0f) || cam->w > 65535.0f || cam->h > 65535.0f || cam->w != std::floor(cam->w) ||
+        cam->h != std::floor(cam->h))
+        return "cam: w/h must be integers in [1, 65535]";
+    if ((uintptr_t)pixels & 3u) return "d_pixels is misaligned (4 bytes)";
+    if ((uintptr_t)max_weight & 3u) return "d_max_weight is misaligned (4 bytes)";
+    if ((uintptr_t)weight_sum & 7u) return "d_weight_sum is misaligned (8 bytes)";
+    if (!pixels && !max_weight && !weight_sum) return "d_pixels, d_max_weight and d_weight_sum are all NULL";
+    return nullptr;
+}
+const char* select_counts_refusal(uint64_t n, const void* counts, uint32_t count_min, uint32_t count_max, uint32_t op, const void* selection) {
+    if (count_min > count_max) return "count_min is above count_max";
+    if (op > SPLAT_SEL_OP_INTERSECT) return "unknown op";
+    if (n >= (1ull << 32)) return "n: too many counts (an index is 32-bit)";
+    if (n && !counts) return "NULL d_counts";
+    if ((uintptr_t)counts & 3u) return "d_counts is misaligned (4 bytes)";
+    if (n && !selection) return "NULL d_selection";
     return nullptr;
 }
 
@@ -877,6 +907,72 @@ int splat_pick_device(splat_ctx* c, const splat_pick_query* q, const splat_camer
     launch_pick(c->stream, c->n, c->planes, c->orig, (const unsigned char*)d_mask, v, *q, n_pixels, d_pixels, bound, pt, d_results, d_layers);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SPLAT_OK;
+}
+
+// The visibility query reads the scene's values, but through a view's tile lists: the scheduler bins the view outside any frame
+// (bin_view_for_query: slot 0's records and tile tables, key buffers of the call's own, freed here) and the kernel walks them.
+int splat_visibility_device(splat_ctx* c, const splat_visibility_query* q, const splat_camera* cam, const void* d_pixel_mask,
+                            const void* d_mask, void* d_pixels, void* d_max_weight, void* d_weight_sum, void* producer_stream) {
+    // (the arguments are judged before the context is looked at, as the pick does it)
+    if (const char* why = visibility_refusal(q, cam, d_pixels, d_max_weight, d_weight_sum)) return fail(c, SPLAT_ERR_INVALID, why);
+    if (!c) return fail(c, SPLAT_ERR_INVALID, "NULL context");
+    if (c->n == 0) return fail(c, SPLAT_ERR_NO_SCENE, "no resident scene to look at");
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    const uint64_t n = c->n;
+    const int W = (int)cam->w, H = (int)cam->h;
+    const int x0 = std::max(q->x0, 0), y0 = std::max(q->y0, 0), x1 = std::min(q->x1, W - 1), y1 = std::min(q->y1, H - 1);
+    const bool empty = x0 > x1 || y0 > y1;
+    int rc = ctx_quiesce(c);                   // (finish_quiet: behind the frames in flight, whatever the region)
+    if (rc != SPLAT_OK) return rc;
+    ViewLists v{};
+    if (!empty) {
+        rc = bin_view_for_query(c, cam, &v);
+        if (rc != SPLAT_OK) return rc;
+    }
+    Temps t(c);
+    t.adopt(v.keys); t.adopt(v.keys2);
+    HIP_TRY(c, follow_producer(c, producer_stream));
+    if (q->op == SPLAT_VIS_SET) {
+        if (d_pixels) HIP_TRY(c, hipMemsetAsync(d_pixels, 0, sizeof(unsigned int) * n, c->stream));
+        if (d_max_weight) HIP_TRY(c, hipMemsetAsync(d_max_weight, 0, sizeof(float) * n, c->stream));
+        if (d_weight_sum) HIP_TRY(c, hipMemsetAsync(d_weight_sum, 0, sizeof(unsigned long long) * n, c->stream));
+    }
+    if (!empty && v.n_pairs != 0) {
+        VisibilityArgs a{};
+        a.s = c->stream; a.W = W; a.tiles_x = v.fc.tiles_x; a.y_up = v.fc.y_up; a.sample_half = v.fc.sample_half;
+        a.x0 = x0; a.y0 = y0; a.x1 = x1; a.y1 = y1; a.weight_min = q->weight_min;
+        a.offsets = v.offsets; a.lens = v.lens; a.keys = v.keys; a.recs = v.recs; a.rect = v.rect; a.orig = c->orig;
+        a.mask = (const unsigned char*)d_mask; a.pixel_mask = (const unsigned char*)d_pixel_mask;
+        a.pixels = (unsigned int*)d_pixels; a.max_weight = (float*)d_max_weight; a.weight_sum = (unsigned long long*)d_weight_sum;
+        launch_visibility(a);
+        HIP_TRY(c, hipGetLastError());
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SPLAT_OK;
+}
+
+// Counts into a selection: launch_neighbour_apply behind an entry point of its own.  No scene is read.
+int splat_select_counts_device(splat_ctx* c, uint64_t n, const void* d_counts, uint32_t count_min, uint32_t count_max, uint32_t op,
+                               void* d_selection, uint64_t* count_out, void* producer_stream) {
+    if (const char* why = select_counts_refusal(n, d_counts, count_min, count_max, op, d_selection)) return fail(c, SPLAT_ERR_INVALID, why);
+    if (!c) return fail(c, SPLAT_ERR_INVALID, "NULL context");
+    if (count_out) *count_out = 0;
+    if (n == 0) return SPLAT_OK;
+    HIP_TRY(c, hipSetDevice(c->cfg.device));
+    int rc = ctx_quiesce(c);
+    if (rc != SPLAT_OK) return rc;
+    Temps t(c);
+    unsigned int* d_count = nullptr;
+    unsigned int count = 0;
+    HIP_TRY(c, t.alloc(&d_count, sizeof(unsigned int)));
+    HIP_TRY(c, hipMemsetAsync(d_count, 0, sizeof(unsigned int), c->stream));
+    HIP_TRY(c, follow_producer(c, producer_stream));
+    launch_neighbour_apply(c->stream, n, (const unsigned int*)d_counts, count_min, count_max, op, (unsigned char*)d_selection, d_count);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(&count, d_count, sizeof count, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (count_out) *count_out = count;
     return SPLAT_OK;
 }
 

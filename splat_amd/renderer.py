@@ -734,6 +734,110 @@ class Renderer:
             if own:
                 self.device_free(pr)
 
+    def _sized_address(self, a, what, size, count):
+        """Device address of a buffer of `count` elements of `size` bytes (None: 0), checked where it describes itself."""
+        if a is None:
+            return 0
+        if not isinstance(a, int) and hasattr(a, "element_size") and int(a.element_size()) != size:
+            raise TypeError("%s: %d-byte elements expected, got %s" % (what, size, getattr(a, "dtype", None)))
+        p = _device_address(a, what, None, int(self.config.device), any_dtype=True)
+        if not isinstance(a, int) and hasattr(a, "numel") and int(a.numel()) != count:
+            raise ValueError("%s: %d elements expected, got %d" % (what, count, int(a.numel())))
+        return p
+
+    def visibility(self, cam_c, *, weight_min=1.0 / 255.0, rect=None, pixel_mask=None, mask=None, pixels=None, max_weight=None,
+                   weight_sum=None, accumulate=False, stream=None):
+        """splat_visibility_device: what each Gaussian contributes to the view of cam_c, occlusion taken into account.  The
+        hits of a pixel and their order are pick's (alpha_min = 0; `mask`: a selection, a Gaussian whose byte is 0 neither
+        counts nor occludes); walking them nearest first with T = 1, hit k has the weight w = T * alpha and leaves
+        T *= 1 - alpha, and it is SEEN at the pixel when w >= weight_min (in [0, 1); 0: every hit of the list).  Over the pixels
+        of rect=(x0, y0, x1, y1) (inclusive, clamped; None: the whole target) whose byte of pixel_mask (a w*h uint8 device
+        image; None: all) is nonzero, the call writes per Gaussian, original index order, into the device buffers given
+        (tensors or addresses, n elements each, at least one):
+            pixels      uint32   on how many pixels it is seen
+            max_weight  float32  its greatest weight (0: seen nowhere)
+            weight_sum  uint64   the sum of int(w * 2**24), truncating -- Q24 fixed point, bit-reproducible
+        accumulate=True adds (and maxes) on top of what the buffers hold instead of zeroing them first: a loop over cameras
+        leaves a Gaussian's importance over the view set on the device.  Exact in every bit.  Synchronous; frames afterwards
+        are the frames they would have been (retained lists and region layouts start over: time only)."""
+        weight_min = float(weight_min)
+        if not (0.0 <= weight_min < 1.0):
+            raise ValueError("weight_min: a number in [0, 1) expected, got %r" % (weight_min,))
+        if pixels is None and max_weight is None and weight_sum is None:
+            raise ValueError("pixels, max_weight, weight_sum: at least one of the three")
+        w, h = int(cam_c.w), int(cam_c.h)
+        x0, y0, x1, y1 = (0, 0, w - 1, h - 1) if rect is None else [int(v) for v in rect]
+        q = _lib.VisibilityQuery(weight_min, x0, y0, x1, y1, _lib.VIS_ACCUMULATE if accumulate else _lib.VIS_SET)
+        dev = int(self.config.device)
+        pp = _byte_mask_address(pixel_mask, "pixel_mask", w * h, dev) if pixel_mask is not None else 0
+        pm = _byte_mask_address(mask, "mask", self.n, dev) if mask is not None else 0
+        pc = self._sized_address(pixels, "pixels", 4, self.n)
+        px = self._sized_address(max_weight, "max_weight", 4, self.n)
+        ps = self._sized_address(weight_sum, "weight_sum", 8, self.n)
+        st = _producer_stream(stream, (pixel_mask, mask, pixels, max_weight, weight_sum))
+        self._check(self._L.splat_visibility_device(self._h, C.byref(q), C.byref(cam_c), C.c_void_p(pp), C.c_void_p(pm), C.c_void_p(pc),
+                                                    C.c_void_p(px), C.c_void_p(ps), C.c_void_p(st)))
+
+    def select_counts(self, counts, selection, at_least=1, at_most=None, op="set", stream=None, n=None):
+        """splat_select_counts_device: Gaussian i passes when at_least <= counts[i] <= at_most (None: no upper end), combined
+        with `selection` by op as select does.  counts: n uint32 in device memory -- visibility's pixels, select_neighbours'
+        counts (n= with plain addresses; default the resident scene's n).  Returns how many are selected after the op."""
+        at_least = int(at_least)
+        at_most = 0xFFFFFFFF if at_most is None else int(at_most)
+        if not (0 <= at_least <= 0xFFFFFFFF and 0 <= at_most <= 0xFFFFFFFF):
+            raise ValueError("at_least / at_most: 32-bit counts expected, got %d and %d" % (at_least, at_most))
+        if at_least > at_most:
+            raise ValueError("at_least (%d) is above at_most (%d): nothing could pass" % (at_least, at_most))
+        if op not in self._SEL_OPS:
+            raise ValueError("op: one of %s, got %r" % (sorted(self._SEL_OPS), op))
+        if n is None:
+            n = int(counts.numel()) if (not isinstance(counts, int) and hasattr(counts, "numel")) else self.n
+        n = int(n)
+        pc = self._sized_address(counts, "counts", 4, n)
+        ps = _byte_mask_address(selection, "selection", n, int(self.config.device))
+        st = _producer_stream(stream, (counts, selection))
+        count = C.c_uint64()
+        self._check(self._L.splat_select_counts_device(self._h, n, C.c_void_p(pc), at_least, at_most, self._SEL_OPS[op], C.c_void_p(ps),
+                                                       C.byref(count), C.c_void_p(st)))
+        return int(count.value)
+
+    def select_visible(self, cams, selection, *, weight_min=1.0 / 255.0, min_pixels=1, rect=None, pixel_mask=None, mask=None, op="set",
+                       stream=None):
+        """What is SEEN: the Gaussians that visibility() finds on at least min_pixels pixels over `cams` -- one camera or a
+        sequence of them, their pixel counts added up in a temporary on the device -- into `selection` by op.  rect,
+        pixel_mask, mask and weight_min are visibility's and apply to every camera.
+            select_visible(cam, sel, pixel_mask=lasso)                  what is seen under the lasso, not the wall behind it
+            select_visible(train_cams, sel); remove(sel, keep=True)     prune what no camera sees
+        Returns how many Gaussians are selected after the op."""
+        if isinstance(cams, _lib.CameraC):
+            cams = [cams]
+        else:
+            try:
+                cams = list(cams)                     # any iterable of cameras: a list, a generator, an object array
+            except TypeError:
+                raise TypeError("cams: a camera (Camera.to_c) or an iterable of them expected, got %s" % type(cams).__name__) from None
+        if not cams:
+            raise ValueError("cams: at least one camera")
+        for cam_c in cams:
+            if not isinstance(cam_c, _lib.CameraC):
+                raise TypeError("cams: every element must be a camera (Camera.to_c), got %s" % type(cam_c).__name__)
+        min_pixels = int(min_pixels)
+        if not 0 <= min_pixels <= 0xFFFFFFFF:
+            raise ValueError("min_pixels: a 32-bit count expected, got %d" % min_pixels)
+        if op not in self._SEL_OPS:
+            raise ValueError("op: one of %s, got %r" % (sorted(self._SEL_OPS), op))
+        _byte_mask_address(selection, "selection", self.n, int(self.config.device))
+        tmp = self._L.splat_device_alloc(self._h, max(4 * self.n, 4))
+        if not tmp:
+            raise SplatError(_lib.ERR_HIP, (self._L.splat_last_error(self._h) or b"select_visible: no device memory for the counts").decode())
+        try:
+            for k, cam_c in enumerate(cams):
+                self.visibility(cam_c, weight_min=weight_min, rect=rect, pixel_mask=pixel_mask, mask=mask, pixels=tmp, accumulate=k > 0,
+                                stream=stream)
+            return self.select_counts(tmp, selection, at_least=min_pixels, op=op, stream=stream, n=self.n)
+        finally:
+            self.device_free(tmp)
+
     def compute_cov3d_device(self, scales, rotations, out, stream=None, n=None):
         """splat_compute_cov3d_device: kernel K0 from device buffers (scales [n,3], rotations [n,4]) into a device buffer
         (out [n,9]); arguments and stream as in upload_device.  Returns when `out` is written."""
